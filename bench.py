@@ -1,6 +1,11 @@
 """UVA training-step throughput on MI355X (BASELINE.json metric: train samples/sec).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config pusht_video] [--batch 32]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and
+prints the result line.  Everything else measured here (the per-kernel trace and roofline passes, the
+host-fed steps, the other configs and precisions, the CPU baseline) runs only with --full.
 
 N > 1: run under torch.distributed.run (RANK / WORLD_SIZE / LOCAL_RANK from the environment),
 or -- when those are unset -- this process spawns N fresh worker processes (one per GPU,
@@ -15,12 +20,17 @@ loss] -> backward (-> RCCL bucket all-reduce inside backward) -> optimizer.step 
 + EMA) -> zero_grad -> lr_scheduler.step -> ema.step.  Weak scaling: batch per GPU fixed.
 
 Timing: W untimed warm-up steps, then exactly K steps between barrier + synchronize pairs, max
-over ranks (`value`, `ms_per_step`), plus the median of the K per-step HIP-event times.  The
-per-kernel trace for `roofline` (HIP events around the traced launches on their stream) runs
-in a separate short pass afterwards, so its event overhead is not in `value`.  At N=1 the
-default run also measures the PushT joint video+action step (BASELINE configs[2] at its
+over ranks (`value`, `ms_per_step`), plus the median of the K per-step HIP-event times.  With
+--full the per-kernel trace for `roofline` (HIP events around the traced launches on their stream)
+runs in a separate short pass afterwards, so its event overhead is not in `value`, and at N=1
+the run also measures the PushT joint video+action step (BASELINE configs[2] at its
 per-GPU batch 64) and reports it under "other_configs" in the same JSON line.
 Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step left its caller
+as DIR/<name>.npy (float32): the loss, the losses of all timed steps, and a fixed seeded sample of
+the updated fp32 master weights, the EMA weights and AdamW's first moment.  Weights, batch and every
+random draw of a step are seeded, so two runs with the same arguments start from identical inputs.
 """
 import argparse
 import json
@@ -56,6 +66,11 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--config", default="pusht_video", choices=sorted(GFLOP_PER_SAMPLE))
     ap.add_argument("--precision", default="bf16", help="bf16 | fp8_attn (fp8 e4m3 attention) | fp32")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the trace / roofline passes, the "
+                         "host-fed steps, --other-configs and the CPU baseline (each still has its own switch below)")
     ap.add_argument("--other-configs",
                     default="pusht_joint:64,libero10_joint:32,umi_multi:56:bf16,umi_multi:56:fp8_attn",
                     help="N=1 only: extra config:batch[:precision] entries measured after the main line "
@@ -135,6 +150,7 @@ def setup_dist(args):
 def build(config, precision, device):
     import copy
 
+    import numpy as np
     import torch
     from unified_video_action_amd import presets
     from unified_video_action_amd.model.autoregressive.ema_model import EMAModel
@@ -143,6 +159,7 @@ def build(config, precision, device):
     from unified_video_action_amd.runtime import RT
     RT.set_precision(precision)
     torch.manual_seed(42)  # identical init on every rank (the reference seeds every rank alike)
+    np.random.seed(42)  # the MAR draws its token orders and mask rate from numpy's global state
     pol = UnifiedVideoActionPolicy(**presets.policy_kwargs(config))
     presets.fit_normalizer(config, pol)
     ema_model = copy.deepcopy(pol)  # workspace:70-72 (before get_optimizer, as the reference)
@@ -196,7 +213,8 @@ def traced_pass(state, steps, only=None):
 
 
 def timed_run(config, batch_size, steps, warmup, precision, device, world, rank):
-    """-> (elapsed s max over ranks, per-step ms list, final loss, (pol, opt, sched, ema, batch))."""
+    """-> (elapsed s max over ranks, per-step ms list, the timed steps' losses (the last one is the final
+    loss), (pol, opt, sched, ema, batch))."""
     import torch
     import torch.distributed as dist
     from unified_video_action_amd import presets
@@ -208,10 +226,11 @@ def timed_run(config, batch_size, steps, warmup, precision, device, world, rank)
     if world > 1:
         dist.barrier()
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+    losses = []
     t0 = time.perf_counter()
     for i in range(steps):
         evs[i][0].record()
-        loss = step(pol, opt, sched, ema, batch)
+        losses.append(step(pol, opt, sched, ema, batch).detach())  # read after the timed region
         evs[i][1].record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
@@ -221,7 +240,34 @@ def timed_run(config, batch_size, steps, warmup, precision, device, world, rank)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     per_step = [a.elapsed_time(b) for a, b in evs]
-    return elapsed, per_step, loss.item(), (pol, opt, sched, ema, batch)
+    return elapsed, per_step, [float(l) for l in losses], (pol, opt, sched, ema, batch)
+
+
+DUMP_SAMPLE = 1 << 21  # elements kept of each flat parameter-sized buffer (8 MiB as float32)
+
+
+def dump_outputs(path, losses, state):
+    """what the last timed step left its caller, as float32 .npy files under `path`: its loss (and the
+    losses of all timed steps), and the same seeded sample of flat positions of the updated fp32 master
+    weights, the EMA weights and AdamW's first moment (the whole buffer where it is not larger)"""
+    import numpy as np
+    import torch
+    pol, opt, sched, ema, batch = state
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), np.asarray(losses[-1:], np.float32))
+    np.save(os.path.join(path, "step_losses.npy"), np.asarray(losses, np.float32))
+    n = opt.store.flat.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        g = torch.Generator(device="cpu").manual_seed(1234)
+        idx = torch.sort(torch.randint(0, n, (DUMP_SAMPLE,), generator=g)).values.to(opt.store.flat.device)
+    for name, buf in (("params", opt.store.flat), ("ema_params", ema.flat), ("adam_exp_avg", opt.m)):
+        if buf is None or buf.numel() != n:
+            raise RuntimeError(f"--dump-outputs: {name} is {'missing' if buf is None else f'{buf.numel()} elements'}, "
+                               f"expected the parameter store's flat layout of {n}")
+        flat = buf.detach().reshape(-1)
+        arr = (flat if idx is None else flat[idx]).float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def h2d_probe(state, device, steps):
@@ -448,14 +494,16 @@ def run(args):
     world, rank, local = setup_dist(args)
     device = torch.device("cuda", local)
     from unified_video_action_amd.native import ops
-    elapsed, per_step, loss, state = timed_run(args.config, args.batch, args.steps, args.warmup, args.precision,
-                                               device, world, rank)
+    elapsed, per_step, losses, state = timed_run(args.config, args.batch, args.steps, args.warmup, args.precision,
+                                                 device, world, rank)
     if rank == 0:
         print(f"[bench] {args.config} B={args.batch}: {args.batch * world * args.steps / elapsed:.2f} samples/s",
               file=sys.stderr, flush=True)
-    main = line_for(args.config, args.batch, world, args.steps, elapsed, per_step, loss)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, losses, state)
+    main = line_for(args.config, args.batch, world, args.steps, elapsed, per_step, losses[-1])
     rows = None
-    if not args.no_trace:
+    if args.full and not args.no_trace:
         # two short traced passes after the timed steps: (1) every library launch between HIP events, for
         # the per-kernel table (the per-launch events add idle time: its step is slower than the timed
         # one, and short kernels read long); (2) events around the roofline kernel's launches only, so
@@ -465,10 +513,10 @@ def run(args):
         roof = next(r for r in rows if r[4] > 0)
         rrows, roof_step_ms = traced_pass(state_, args.trace_steps, only=[roof[1]])
         roof = rrows[0]
-    h2d = h2d_probe(state, device, args.h2d_steps) if (world == 1 and args.h2d_steps > 0) else None
+    h2d = h2d_probe(state, device, args.h2d_steps) if (args.full and world == 1 and args.h2d_steps > 0) else None
     del state
     others = []
-    if world == 1 and args.other_configs:
+    if args.full and world == 1 and args.other_configs:
         for item in args.other_configs.split(","):
             cfg, b, prec = (item.split(":") + ["", ""])[:3]
             b = int(b or args.batch)
@@ -476,7 +524,7 @@ def run(args):
             torch.cuda.empty_cache()
             e, ps, lo, st = timed_run(cfg, b, args.other_steps, args.warmup, prec, device, world, rank)
             del st
-            others.append(dict(line_for(cfg, b, world, args.other_steps, e, ps, lo), steps=args.other_steps,
+            others.append(dict(line_for(cfg, b, world, args.other_steps, e, ps, lo[-1]), steps=args.other_steps,
                                precision=prec))
             print(f"[bench] {cfg} B={b} {prec}: {others[-1]['value']} samples/s", file=sys.stderr, flush=True)
         from unified_video_action_amd.runtime import RT
@@ -550,7 +598,7 @@ def run(args):
         out["h2d"] = h2d
     if others:
         out["other_configs"] = others
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     print(json.dumps(out), flush=True)
     if world > 1:

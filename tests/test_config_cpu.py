@@ -1,7 +1,6 @@
 """Hydra-style composition without hydra (unified_video_action_amd/config.py): this build's
 config tree, command-line overrides, interpolation, the restricted ${eval:} resolver, target
-mapping -- and, when the reference checkout is present in this container, the reference's own
-config tree (train.py --config-dir=<reference>/unified_video_action/config)."""
+mapping."""
 import os
 
 import pytest
@@ -9,7 +8,6 @@ import pytest
 from unified_video_action_amd import config as C
 
 OWN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "unified_video_action_amd", "config")
-REF = "/root/reference/unified_video_action/config"
 
 
 def test_own_configs_compose():
@@ -51,17 +49,3 @@ def test_targets_map_to_this_build():
     assert ws.__module__.startswith("unified_video_action_amd.")
     with pytest.raises(ImportError):
         C.get_class("unified_video_action.dataset.pusht_image_dataset.PushTImageDataset")
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
-@pytest.mark.parametrize("name", ["uva_pusht.yaml", "uva_libero10.yaml", "uva_umi_multi.yaml", "uva_umi.yaml",
-                                  "uva_toolhang.yaml", "uva_human_pp.yaml"])
-def test_reference_config_tree_composes(name):
-    c = C.compose(REF, name, ["training.debug=true"])
-    assert C.get_class(c.model.policy._target_).__module__ == \
-        "unified_video_action_amd.policy.unified_video_action_policy"
-    assert C.get_class(c.model._target_).__name__ == "TrainUnifiedVideoActionWorkspace"
-    assert c.model.policy.shape_meta == c.task.shape_meta
-    if name == "uva_umi_multi.yaml":  # umi_lazy@dataset package default + ${eval:...} resolvers
-        ds = c.task.dataset
-        assert isinstance(ds.dataset_configs, dict) and len(ds.dataset_configs) == 3

@@ -6,7 +6,7 @@ OUT=${1:-gpurun_out/r02}
 mkdir -p $OUT
 run() {  # name, args...
   local name=$1; shift
-  timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --other-configs '' --no-trace "$@" \
+  timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --other-configs '' --no-trace "$@" \
     > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "FAIL $name"; tail -5 $OUT/bench_$name.err; exit 1; }
   cat $OUT/bench_$name.json
 }

@@ -7,6 +7,6 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o run -- \
-  python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --other-configs "" > $OUT/bench.json 2> $OUT/bench.err
+  python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --other-configs "" > $OUT/bench.json 2> $OUT/bench.err
 find $OUT/kt -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
 echo done
