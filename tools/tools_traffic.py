@@ -15,8 +15,8 @@ import os
 import sys
 
 # bench tag -> list of (kernel-name substring, grid size or None); a tag whose launches run ONE of
-# several kernels (the GN convs: with a residual on conv3x3_halo, without on the persistent
-# conv3x3_gn_pt) is in MEAN: its per-launch traffic is the launch-weighted mean.  The persistent
+# several kernels (the GN convs: with a residual on conv3x3_halo_gn, without on the persistent
+# conv3x3_gn_pt; "conv3x3_halo" matches conv3x3_halo_plain and conv3x3_halo_gn) is in MEAN: its per-launch traffic is the launch-weighted mean.  The persistent
 # kernel's grid is the same at every level (2 workgroups per CU): its launches are told apart by
 # size (("size", k): the k-th largest quarter... see split_pt)
 MEAN = {"conv3x3/s1 bf16 256x256 Ci128 Co128 n256", "conv3x3/s1 bf16 128x128 Ci128 Co128 n256"}

@@ -123,13 +123,6 @@ __device__ __forceinline__ void stage_store(bf16* lds, const bf16x8 (&r)[2]) {
   }
 }
 
-// workgroup barrier that orders LDS only: outstanding global loads / atomics stay in flight
-// (__syncthreads would drain vmcnt, i.e. wait for every dQ atomic of the tile)
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 __device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
 // keep-bit b of a mask word as an all-ones / all-zeros 32-bit mask.  (A v_bfe_i32 in inline asm
 // saves hipcc's v_and + v_cmp + v_cndmask lowering but measured slower in the dK/dV loop: the

@@ -47,7 +47,6 @@ __device__ __forceinline__ float group16_max(float v) {
   return v;
 }
 
-// ---- counter-based dropout mask (identical in forward and backward kernels) ------------
 // ---- dropout mask ----------------------------------------------------------------------
 // Stateless counter-based mask shared by every kernel that drops (GEMM epilogues, attention
 // fwd/bwd, softmax, activation backward), so forward and backward regenerate identical masks.
@@ -76,13 +75,7 @@ __device__ __forceinline__ uint32_t drop_mix(uint32_t x) {
   return x;
 }
 __device__ __forceinline__ uint32_t drop_hash(uint32_t key, uint64_t pair) {
-  uint32_t x = drop_first(key, pair);
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
+  return drop_mix(drop_first(key, pair));
 }
 __device__ __forceinline__ bool dropout_keep(uint64_t seed, uint64_t idx, uint32_t thresh) {
   const uint32_t h = drop_hash(drop_key(seed), idx >> 1);
@@ -176,7 +169,14 @@ __device__ __forceinline__ float act_grad(int act, float x) {
   }
 }
 
-// ---- launch error plumbing -----------------------------------------------------------
+// ---- workgroup placement and barriers -------------------------------------------------
+// XCD-aware logical id of a 1-D grid's block: the hardware deals linear workgroup ids round-robin over
+// the 8 XCDs; the remap is bijective and gives the blocks that share an XCD (bid % 8) a contiguous
+// range of logical ids, so neighbouring tiles share one XCD's L2
+__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
+  const int q = nblk / 8, r = nblk % 8, x = bid % 8;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
+}
 // XCD-aware (x, y) of a 2-D grid.  The hardware deals linear workgroup ids (x fastest) round-robin
 // over the 8 XCDs, so the gridDim.x blocks of one y (one attention head: its K/V or Q/dO rows are
 // re-read by every one of them) would land on 8 different L2s.  The remap gives each XCD a
@@ -201,5 +201,14 @@ __device__ __forceinline__ float row16_sum(float v) {
   return v;
 }
 
+// workgroup barrier that orders LDS only: global loads, stores and atomics stay in flight across it
+// (__syncthreads drains vmcnt too, i.e. waits for every outstanding store of the tile)
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+// ---- launch error plumbing -----------------------------------------------------------
 #define UVA_LAUNCH_CHECK() \
   do { hipError_t _e = hipGetLastError(); if (_e != hipSuccess) return (int)_e; } while (0)

@@ -293,12 +293,6 @@ __device__ __forceinline__ bf16x8 frag_load(const bf16* lds, int row0, int ks) {
   }
 }
 
-__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
-  // bijective: blocks that share an XCD (bid % 8) get a contiguous range of logical ids
-  int q = nblk / 8, r = nblk % 8, x = bid % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-}
-
 // one row segment of 8 consecutive columns (16-B aligned in C): the row-wise epilogue inputs (C for
 // beta, residual, gate) are loaded by epi_load_row8 and consumed by epi_apply_row8, so a caller can
 // issue the next row's loads before this row's store -- a load issued after a store waits for that
@@ -452,13 +446,6 @@ __device__ __forceinline__ void epi_row8(TC* __restrict__ C, long long cbase, co
 // 8 consecutive columns x 8 rows with 16-B vector loads/stores (coalesced, issue-light).
 #define EPI_TP 132  // fp32 row pitch of the staged tile (+4 floats: conflict-free column writes)
 #define EPI_LDS_BYTES (128 * EPI_TP * 4 + 4 * 16 * 8 * 2 * 4)
-
-// epilogue barrier that orders LDS only: the chunk's global stores stay in flight across it
-__device__ __forceinline__ void epi_lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 template <typename TC>
 __device__ __forceinline__ void epilogue_tile(const f32x4 (&acc)[4][4], char* smem, TC* __restrict__ C, int M, int N,
@@ -1238,7 +1225,7 @@ __global__ __launch_bounds__(512, 1) void gemm_8ph(const bf16* __restrict__ A, c
           for (int r = 0; r < 4; ++r)
             T[(rbase + i * 16 + (lane >> 4) * 4 + r) * G::TP + wc * G::RWB + j * 16 + (lane & 15)] = acc[i][j][r];
     }
-    if constexpr (VAR & 64) __syncthreads(); else epi_lds_barrier();
+    if constexpr (VAR & 64) __syncthreads(); else lds_barrier();
     constexpr int NIT = (ER + RPP - 1) / RPP;
     const int rowb = m0 + chunk * ER + rsub;
     const int rowe = min(M, m0 + chunk * ER + ER);  // rows of this chunk (rl < ER)
@@ -1418,7 +1405,7 @@ __global__ __launch_bounds__(512, 1) void gemm_8ph(const bf16* __restrict__ A, c
             red[((wid * C8 + lane) * 8 + e) * 2 + 1] = gs_q[e];
           }
         }
-        if constexpr (VAR & 64) __syncthreads(); else epi_lds_barrier();
+        if constexpr (VAR & 64) __syncthreads(); else lds_barrier();
         const int gsz = N / 32;
         const int ngroups = min(BN, N - n0) / gsz;
         if ((int)threadIdx.x < ngroups && m0 + chunk * ER < M) {
@@ -1437,7 +1424,7 @@ __global__ __launch_bounds__(512, 1) void gemm_8ph(const bf16* __restrict__ A, c
     }
     // LDS-only: the stores of this chunk stay in flight (a __syncthreads() would drain them), and
     // after the last chunk nothing reads T again
-    if constexpr (VAR & 64) __syncthreads(); else if (chunk == 0) epi_lds_barrier();
+    if constexpr (VAR & 64) __syncthreads(); else if (chunk == 0) lds_barrier();
   }
 }
 

@@ -66,11 +66,6 @@ struct G4Cfg {
   static constexpr int A_BYTES = BM * 128, REGION = (BM + BN) * 128, RING = 2 * REGION;
 };
 
-__device__ __forceinline__ int g4_xcd_remap(int bid, int nblk) {
-  const int q = nblk / 8, r = nblk % 8, x = bid % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-}
-
 // 16-B chunk swizzle of a k-major image row [64 k][W] (T = 1 operands), chosen so that the 8 rows
 // {8g + q} a 32-lane group of ds_read_b64_tr_b16 touches (32 B each) fall on 8 distinct 32-B bank
 // slots: 512-B rows (W = 256) all start on one bank -> XOR by 8 distinct even chunk offsets; 384-B rows
@@ -108,7 +103,7 @@ __global__ __launch_bounds__(256, 1) void gemm_4w(const bf16* __restrict__ A, co
   const int tm = (M + G::BM - 1) / G::BM, tn = (N + G::BN - 1) / G::BN, ntiles = tm * tn;
   const int nitems = ntiles * splits;
   const int grid = gridDim.x;
-  const int slot = g4_xcd_remap(blockIdx.x, grid);
+  const int slot = xcd_remap(blockIdx.x, grid);
   if (slot >= nitems) return;
   const int my_items = (nitems - slot + grid - 1) / grid;
 

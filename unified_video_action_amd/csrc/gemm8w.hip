@@ -51,11 +51,6 @@ struct G8Cfg {
   static_assert(GA * 8 * NW == BM && GB * 8 * NW == BN, "DMA split");
 };
 
-__device__ __forceinline__ int g8_xcd_remap(int bid, int nblk) {
-  const int q = nblk / 8, r = nblk % 8, x = bid % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-}
-
 // 16-B chunk swizzle of a k-major image row [64 k][W] (TA / TB = 1 operands), as gemm4.hip's: the 8 rows a
 // 32-lane group of ds_read_b64_tr_b16 touches fall on distinct 32-B bank slots
 template <int W>
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_8w(const bf16* __restric
   const int tm = (M + G::BM - 1) / G::BM, tn = (N + G::BN - 1) / G::BN, ntiles = tm * tn;
   const int nitems = ntiles * splits;
   const int grid = gridDim.x;
-  const int slot = g8_xcd_remap(blockIdx.x, grid);
+  const int slot = xcd_remap(blockIdx.x, grid);
   if (slot >= nitems) return;
   const int my_items = (nitems - slot + grid - 1) / grid;
 
