@@ -11,8 +11,14 @@ Mlp.fc1 -> GELU -> drop -> fc2 -> drop, + the Block's residual add), through the
 * ragged M / N edges (masked stores, zero-filled operand rows), several tiles per workgroup, K = 256;
 * a whole timm Block (functional.BlockFn) forward + backward with the fused routes (the defaults) against the
   split routes: output and every gradient bit-identical except fc1.bias (fp32 summation order, 1e-5).
-Reference for the math: the split route, itself pinned to torch fp32 / the reference's goldens
-(test_kernels_gpu.py, test_parity_gpu.py)."""
+Reference for the math of the cases above: the split route, itself pinned to torch fp32 / the reference's goldens
+(test_kernels_gpu.py, test_parity_gpu.py).
+* (second half of the file) the three fused epilogues element by element against fp64 math on the same bf16
+  operands under the dropout mask restated in oracle/dropmask.py -- nothing there comes from another kernel --
+  and 16 repeat launches of each, bit-identical and right."""
+import functools
+import math
+
 import pytest
 import torch
 
@@ -291,3 +297,210 @@ def test_dw_8w_tt_vs_routes(M, N, K, beta):
     tiles = ((M + 255) // 256) * ((N + 191) // 192)
     if tiles <= 16 and K % 128 == 0 and K >= 256 and M >= 256 and N >= 192:
         assert torch.equal(d8, d4)
+
+
+# =====================================================================================================
+# The fused epilogues against fp64 math, element by element, under the dropout mask restated in
+# oracle/dropmask.py (pinned to csrc/common.h by tests/test_dropmask_cpu.py) -- no mask and no value here
+# comes from another kernel of this library.
+#
+# Tolerance per element (each part derived, none tuned or widened):
+#   |out - ref| <= r * 2^-8 * |rounded value| + 2e-5 * max|product| + a_gelu
+# * r bf16 roundings lie between the fp64 reference and the stored value; half a bf16 ulp is at most 2^-8 of
+#   the value (8 significand bits).  The rounded value is the reference itself except in EPI 2, where the bf16
+#   rounding acts on the product before the fp32 residual is added: there it is keep * scale * product, not
+#   R + keep * scale * product (which can be arbitrarily smaller than what was rounded);
+# * 2e-5 of the product's scale: the fp32-accumulation pin of the MFMA GEMMs (test_gemm4_fp32_pin_vs_fp64);
+# * a_gelu: erf_fast's stated 1.5e-7 absolute error (common.h, A&S 7.1.26) times the factor the erf
+#   multiplies: scale * x / 2 in GELU + dropout, scale * product / 2 in dropout + GELU'.
+# A NaN (an element the kernel never stored: every output starts NaN-filled) is over tolerance.
+# =====================================================================================================
+BF_HALF_ULP = 2.0 ** -8
+ACC_PIN = 2e-5
+ERF_ABS = 1.5e-7
+P64_SEED = 0x9E3779B97F4A7C15 * 77 + 0xBF58476D1CE4E5B9 & 0xFFFFFFFFFFFFFFFF  # a seed with high bits set
+
+
+def _b2b_M(N):
+    """smallest M at which gemm_8w has more tiles than workgroups in BOTH launch forms (g8_launch1: grid =
+    min(tiles, CUs * 8 / NW); tiles of 256 x 192 at NW = 8, 128 x 192 at NW = 4), + 199 rows so the tiles that
+    run second in a workgroup (the last row tile's) are not one row tall; both conditions are monotone in M"""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    tn = (N + 191) // 192
+    M = 256
+    while not (-(-M // 256) * tn > cus and -(-M // 128) * tn > 2 * cus):
+        M += 1
+    return M + 199
+
+
+def _fp64_shapes():
+    return [(256, 192, 256), (300, 200, 256), (1000, 776, 384), (_b2b_M(776), 776, 256)]
+
+
+FP64_SHAPE_IDS = ["one_tile", "ragged", "multi_tile", "back_to_back"]
+
+
+@pytest.fixture(params=range(4), ids=FP64_SHAPE_IDS)
+def shape64(request):
+    return _fp64_shapes()[request.param]
+
+
+@functools.lru_cache(maxsize=None)
+def _keep_scale(M, N, p):
+    import dropmask
+    th, scale = dropmask.drop_params(p)
+    if th == 0:
+        return torch.ones(M, N, dtype=torch.bool, device=DEV), 1.0
+    return torch.from_numpy(dropmask.keep_flat(P64_SEED, M, N, th)).to(DEV), scale
+
+
+def _gelu64(x):
+    return 0.5 * x * (1.0 + torch.erf(x * (1.0 / math.sqrt(2.0))))
+
+
+def _dgelu64(x):
+    return 0.5 * (1.0 + torch.erf(x * (1.0 / math.sqrt(2.0)))) + x * torch.exp(-0.5 * x * x) * (1.0 / math.sqrt(2.0 * math.pi))
+
+
+@functools.lru_cache(maxsize=None)
+def _case64(which, M, N, K):
+    """operands (bf16) and the fp64 product on those operands, made once per (epilogue, shape)"""
+    g = torch.Generator(device=DEV).manual_seed({"fc1": 1, "fc2": 2, "dgelu": 3, "plain": 4}[which] * 100003 + M + N + K)
+    if which == "dgelu":
+        a, w = (torch.randn(M, K, device=DEV, generator=g) * 0.1).to(torch.bfloat16), _rand(N, K, 0.05, g=g)
+        extra = (torch.randn(M, N, device=DEV, generator=g) * 1.5).to(torch.bfloat16)  # the saved pre-activation
+        prod = a.double() @ w.double().t()
+        return a, w, None, extra, prod
+    a, w = _rand(M, K, g=g), _rand(N, K, 0.1, g=g)
+    b = torch.rand(N, device=DEV, generator=g) * 0.2 - 0.1
+    extra = torch.randn(M, N, device=DEV, generator=g) if which == "fc2" else None  # the fp32 residual
+    prod = a.double() @ w.double().t() + b.double()
+    return a, w, b, extra, prod
+
+
+def _within(got, ref, tol, what):
+    """every element of got within tol of ref; a NaN in got (never stored, or computed as NaN) fails"""
+    err = (got.double() - ref).abs()
+    bad = ~(err <= tol)
+    if bad.any():
+        nan = int(got.isnan().sum())
+        i = torch.where(bad, torch.nan_to_num(err - tol, nan=float("inf")), torch.full_like(err, -float("inf"))).argmax().item()
+        r, c = divmod(i, got.shape[1])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements over tolerance ({nan} of them NaN: "
+                             f"not stored, or computed as NaN); worst at ({r}, {c}): got {got[r, c].item()!r} "
+                             f"ref {ref[r, c].item()!r} tol {tol[r, c].item():.3e}")
+
+
+def _run_fc1(M, N, K, p):
+    from unified_video_action_amd.native import ops
+    x, w, b, _, _ = _case64("fc1", M, N, K)
+    pre = torch.full((M, N), float("nan"), device=DEV, dtype=torch.bfloat16)
+    out = torch.full_like(pre, float("nan"))
+    assert ops.linear_gelu_drop(x, w, b, pre, out, drop_p=p, seed=P64_SEED)
+    return pre, out
+
+
+def _check_fc1(M, N, K, p, pre, out):
+    prod = _case64("fc1", M, N, K)[4]
+    keep, scale = _keep_scale(M, N, p)
+    _within(pre, prod, BF_HALF_ULP * prod.abs() + ACC_PIN * prod.abs().max(), "EPI 1 pre_out")
+    # the second rounding on its own: GELU + dropout of the STORED pre_out
+    x = pre.double()
+    ref = torch.where(keep, scale * _gelu64(x), torch.zeros_like(x))
+    _within(out, ref, BF_HALF_ULP * ref.abs() + ERF_ABS * 0.5 * x.abs() * scale, "EPI 1 out")
+    assert (out.view(torch.int16)[~keep] == 0).all()  # dropped: +0, not -0
+    assert (out[keep & (ref.abs() > 1e-30)] != 0).all()
+
+
+def _run_fc2(M, N, K, p):
+    from unified_video_action_amd.native import ops
+    x, w, b, res, _ = _case64("fc2", M, N, K)
+    out = torch.full((M, N), float("nan"), device=DEV)
+    assert ops.linear_drop_res(x, w, b, res, out, drop_p=p, seed=P64_SEED)
+    return (out,)
+
+
+def _check_fc2(M, N, K, p, out):
+    _, _, _, res, prod = _case64("fc2", M, N, K)
+    keep, scale = _keep_scale(M, N, p)
+    branch = torch.where(keep, scale * prod, torch.zeros_like(prod))
+    ref = res.double() + branch
+    tol = BF_HALF_ULP * branch.abs() + ACC_PIN * prod.abs().max()
+    _within(out, ref, tol, "EPI 2 out")
+    assert torch.equal(out[~keep].view(torch.int32), res[~keep].view(torch.int32))  # dropped: R bit for bit
+
+
+def _run_dgelu(M, N, K, p):
+    from unified_video_action_amd.native import ops
+    dy, wt, _, pre, _ = _case64("dgelu", M, N, K)
+    dpre = torch.full((M, N), float("nan"), device=DEV, dtype=torch.bfloat16)
+    db = torch.full((N,), 0.5, device=DEV)
+    assert ops.linear_dgelu_drop(dy, wt, pre, dpre, db, drop_p=p, seed=P64_SEED)
+    return dpre, db
+
+
+def _check_dgelu(M, N, K, p, dpre, db):
+    _, _, _, pre, prod = _case64("dgelu", M, N, K)
+    keep, scale = _keep_scale(M, N, p)
+    x = pre.double()
+    gp = _dgelu64(x)
+    da = torch.where(keep, scale * prod, torch.zeros_like(prod))
+    ref = gp * da
+    tol = 2 * BF_HALF_ULP * ref.abs() + ACC_PIN * prod.abs().max() + 0.5 * ERF_ABS * da.abs()
+    _within(dpre, ref, tol, "EPI 3 dpre")
+    assert (dpre[~keep] == 0).all()
+    want = dpre.double().sum(0) + 0.5
+    assert (db.double() - want).abs().max().item() < 1e-5 * want.abs().max().item()
+
+
+_FUSED = {"fc1": (_run_fc1, _check_fc1), "fc2": (_run_fc2, _check_fc2), "dgelu": (_run_dgelu, _check_dgelu)}
+
+
+@pytest.mark.parametrize("p", [0.0, 0.1])
+@pytest.mark.parametrize("which", ["fc1", "fc2", "dgelu"])
+def test_fused_epilogue_vs_fp64(which, shape64, p, form):
+    """EPI 1 / 2 / 3 of gemm_8w, every element against fp64 math on the same bf16 operands under the restated
+    mask (tolerance: the comment block above)"""
+    M, N, K = shape64
+    run, check = _FUSED[which]
+    check(M, N, K, p, *run(M, N, K, p))
+
+
+def _repeat16(run, check, M, N, K, what):
+    outs = [run(M, N, K, 0.1) for _ in range(16)]
+    torch.cuda.synchronize()
+    for i, o in enumerate(outs[1:], 1):
+        for a, b0 in zip(o, outs[0]):
+            assert torch.equal(a, b0), (what, i, (a != b0).nonzero()[:4].tolist())
+    check(M, N, K, 0.1, *outs[0])
+
+
+@pytest.mark.parametrize("which", ["fc1", "fc2", "dgelu"])
+def test_fused_repeat_launches_identical_and_right(which, form):
+    """16 launches of one product into 16 distinct NaN-filled outputs: all bit-identical, the first one right
+    against fp64.  (EPI 3 once returned a zeroed element in 7 of 16 launches, in a different place each time:
+    DESIGN.md "A compiler hazard found on the way"; a test that launches each shape once misses that.)  A
+    determinism check on values, like test_gemm4_repeatable -- not a stress loop."""
+    _repeat16(*_FUSED[which], 1000, 776, 384, which)
+
+
+def test_gemm4_repeat_launches_identical_and_right():
+    """the same for the plain gemm_4w bf16 product, which has the same permlane16_swap gather"""
+    from unified_video_action_amd.native import ops
+    M, N, K = 1000, 776, 384
+    assert ops.gemm4_plan(M, N, K) is not None
+    x, w, b, _, prod = _case64("plain", M, N, K)
+
+    def run(*_):
+        y = torch.full((M, N), float("nan"), device=DEV, dtype=torch.bfloat16)
+        ops.linear(x, w, y, bias=b)
+        return (y,)
+
+    def check(M, N, K, p, y):
+        _within(y, prod, BF_HALF_ULP * prod.abs() + ACC_PIN * prod.abs().max(), "gemm_4w bf16")
+
+    prev = ops.gemm8w_set(0, -2)  # plain products on gemm_4w, whatever an earlier test's RT.begin_forward() left
+    try:
+        _repeat16(run, check, M, N, K, "gemm_4w")
+    finally:
+        ops.gemm8w_set(prev[0], -2)

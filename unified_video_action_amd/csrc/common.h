@@ -63,10 +63,10 @@ __host__ __device__ __forceinline__ uint32_t drop_key(uint64_t seed) {
 }
 // drop_hash = drop_mix(first word); split so a caller hashing pairs base..base+31 of a 32-aligned
 // base can form the first word as (base's first word) ^ j
-__device__ __forceinline__ uint32_t drop_first(uint32_t key, uint64_t pair) {
+__host__ __device__ __forceinline__ uint32_t drop_first(uint32_t key, uint64_t pair) {
   return (uint32_t)pair ^ (key + __builtin_rotateleft32((uint32_t)(pair >> 32), 11));
 }
-__device__ __forceinline__ uint32_t drop_mix(uint32_t x) {
+__host__ __device__ __forceinline__ uint32_t drop_mix(uint32_t x) {
   x ^= x >> 16;
   x *= 0x7feb352du;
   x ^= x >> 15;
@@ -74,10 +74,10 @@ __device__ __forceinline__ uint32_t drop_mix(uint32_t x) {
   x ^= x >> 16;
   return x;
 }
-__device__ __forceinline__ uint32_t drop_hash(uint32_t key, uint64_t pair) {
+__host__ __device__ __forceinline__ uint32_t drop_hash(uint32_t key, uint64_t pair) {
   return drop_mix(drop_first(key, pair));
 }
-__device__ __forceinline__ bool dropout_keep(uint64_t seed, uint64_t idx, uint32_t thresh) {
+__host__ __device__ __forceinline__ bool dropout_keep(uint64_t seed, uint64_t idx, uint32_t thresh) {
   const uint32_t h = drop_hash(drop_key(seed), idx >> 1);
   return ((idx & 1) ? (h >> 16) : (h & 0xFFFFu)) >= thresh;
 }
