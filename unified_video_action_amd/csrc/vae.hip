@@ -61,14 +61,17 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
   for (int c0 = 0; c0 < C; c0 += 256) {
     const int c = c0 + (threadIdx.x % min(C, 256));
     const int pl = threadIdx.x / min(C, 256);
+    // when 256 % C != 0 (C = 96, 160, 192, 224) the threads past tpc * C form a partial lane group with
+    // pl == tpc, whose pixels p0 + tpc, p0 + 2 tpc, ... lane group 0 already sums: it contributes nothing
+    const bool live = c < C && pl < tpc;
     float s = 0.f, q = 0.f;
-    if (c < C)
+    if (live)
       for (int p = p0 + pl; p < p1; p += tpc) {
         float v = to_f32(x[((long long)n * HW + p) * C + c]);
         s += v;
         q += v * v;
       }
-    if (c < C) {
+    if (live) {
       atomicAdd(&red[0][c], s);
       atomicAdd(&red[1][c], q);
     }
