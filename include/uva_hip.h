@@ -348,6 +348,23 @@ int uva_attn_bwd_bias(const void* qkv, const void* out, const void* dout, const 
                       float* Dvec, void* dqkv, float* dbias, int accum, float* part, int B, int N, int H, float scale,
                       float drop_p, hipStream_t stream);
 
+/* ---- fused attention, head_dim 80 and 128, bf16 (the mar_huge and mar_tiny / mar_small presets'
+ *      timm Attention / SDPA with attn dropout, mar_con_unified.py:201-249; csrc/attention_hd.hip).
+ *      Tensors as uva_attn_fwd / uva_attn_bwd with head_dim in place of 64: qkv / dqkv [B,N,3,H,head_dim],
+ *      out / dout [B,N,H,head_dim], lse2 / Dvec [B,H,N]; mask = the uva_attn_dropmask planes (the keep
+ *      decision does not depend on head_dim).  N % 64 == 0.  An unsupported head_dim or N, or drop_p > 0
+ *      with a null mask, returns hipErrorInvalidValue before any launch.
+ * uva_attn_hd_supported: pure host, 1 for head_dim 80 and 128, else 0 (64 is uva_attn_fwd's).
+ * uva_attn_bwd_hd: dbias[3 H head_dim] (may be NULL) (+)= column sums of dqkv as stored (the qkv Linear's bias
+ *      gradient) through `part` (uva_attn_bwd_hd_part_floats floats, pure host; unused when dbias is NULL). */
+int uva_attn_hd_supported(int head_dim);
+int uva_attn_fwd_hd(const void* qkv, void* out, float* lse2, const void* mask, int B, int N, int H, int head_dim,
+                    float scale, float drop_p, hipStream_t stream);
+long long uva_attn_bwd_hd_part_floats(int B, int N, int H, int head_dim);
+int uva_attn_bwd_hd(const void* qkv, const void* out, const void* dout, const float* lse2, const void* mask,
+                    float* Dvec, void* dqkv, float* dbias, int accum, float* part, int B, int N, int H, int head_dim,
+                    float scale, float drop_p, hipStream_t stream);
+
 /* ---- KL-VAE encoder plumbing (vae/vaekl.py, utils/data_utils.py) ---------------------
  * uva_resize_select: obs image [B,T,3,Hin,Win] fp32 in [0,1] -> NHWC [B*nsel,256,256,Cpad]
  *   frames sel[] (select_frames, data_utils.py:140-158), bilinear align_corners=False

@@ -165,9 +165,10 @@ __global__ __launch_bounds__(256) void ln_bwd(const TI* __restrict__ x, const fl
                                               TO* __restrict__ dscale, TO* __restrict__ dshift,
                                               float* __restrict__ dw_part, float* __restrict__ db_part, int rows,
                                               int D, int rows_per_block, LnDrop ldrop = LnDrop{}) {
-  __shared__ float red_w[4][1024];
-  __shared__ float red_b[4][1024];
-  __shared__ float red_d[DROPO ? 4 : 1][DROPO ? 1024 : 1];
+  constexpr int RW = VEC * NC * 64 > 1024 ? VEC * NC * 64 : 1024;  // 1024 for every D <= 1024 form
+  __shared__ float red_w[4][RW];
+  __shared__ float red_b[4][RW];
+  __shared__ float red_d[DROPO ? 4 : 1][DROPO ? RW : 1];
   float pd[NC][VEC];
   if constexpr (DROPO) {
 #pragma unroll
@@ -487,6 +488,10 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const T* __restrict__ 
       ln_bwd<TI, TO, 4, 4, TD><<<grid, 256, 0, stream>>>(__VA_ARGS__);                       \
     } else if (D <= 1024) {                                                                  \
       ln_bwd<TI, TO, 1, 16, TD><<<grid, 256, 0, stream>>>(__VA_ARGS__);                      \
+    } else if (D % 256 == 0 && D <= 1280) { /* mar_huge's width: five 4-wide chunks per lane */ \
+      ln_bwd<TI, TO, 4, 5, TD><<<grid, 256, 0, stream>>>(__VA_ARGS__);                       \
+    } else if (D % 256 == 0 && D <= 2048) {                                                  \
+      ln_bwd<TI, TO, 4, 8, TD><<<grid, 256, 0, stream>>>(__VA_ARGS__);                       \
     } else {                                                                                 \
       return (int)hipErrorInvalidValue;                                                      \
     }                                                                                        \
@@ -500,6 +505,10 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const T* __restrict__ 
       KERNEL<TI, TO, 4, 4><<<grid, 256, 0, stream>>>(__VA_ARGS__);                           \
     } else if (D <= 1024) {                                                                  \
       KERNEL<TI, TO, 1, 16><<<grid, 256, 0, stream>>>(__VA_ARGS__);                          \
+    } else if (D % 256 == 0 && D <= 1280) { /* mar_huge's width: five 4-wide chunks per lane */ \
+      KERNEL<TI, TO, 4, 5><<<grid, 256, 0, stream>>>(__VA_ARGS__);                           \
+    } else if (D % 256 == 0 && D <= 2048) {                                                  \
+      KERNEL<TI, TO, 4, 8><<<grid, 256, 0, stream>>>(__VA_ARGS__);                           \
     } else {                                                                                 \
       return (int)hipErrorInvalidValue;                                                      \
     }                                                                                        \

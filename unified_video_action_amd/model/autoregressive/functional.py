@@ -230,7 +230,7 @@ class ActFn(torch.autograd.Function):
 # attention
 # --------------------------------------------------------------------------------------
 def _attn_mat_fwd(qkv, B, N, H, scale, p, seed):
-    """materialised attention in fp32 (parity path / head_dim != 64): S=QK^T, P=softmax, O=P V."""
+    """materialised attention in fp32 (parity path / head_dim other than 64, 80, 128): S=QK^T, P=softmax, O=P V."""
     D = qkv.shape[1] // 3
     hd = D // H
     ld = 3 * D
@@ -272,7 +272,9 @@ def _attn_mat_bwd(qkv, P, Pd, dO, B, N, H, scale, p, seed):
 
 
 def use_flash(N, hd=64):
-    return cdt() == torch.bfloat16 and RT.flash_attention and N % 64 == 0 and hd == 64
+    """does the Block take the fused bf16 attention?  head_dim 64: csrc/attention.hip; 80 and 128 (the mar_huge
+    and mar_tiny / mar_small presets): csrc/attention_hd.hip.  fp32 precision keeps the materialised route."""
+    return cdt() == torch.bfloat16 and RT.flash_attention and N % 64 == 0 and hd in (64, 80, 128)
 
 
 # --------------------------------------------------------------------------------------
@@ -302,7 +304,14 @@ class BlockFn(torch.autograd.Function):
         qkv = torch.empty(M, 3 * D, dtype=c, device=dev)
         linear_bias(h1, qkvw, qkvb, qkv)
         flash = use_flash(N, D // H)
-        if flash:
+        if flash and D // H != 64:
+            # head_dim 80 / 128: the bf16 kernels of csrc/attention_hd.hip (also under fp8_attn: there is no
+            # fp8 kernel at these widths); the keep-mask planes do not depend on head_dim
+            o = torch.empty(M, D, dtype=c, device=dev)
+            lse = torch.empty(B, H, N, dtype=F32, device=dev)
+            pm = premask[1] if premask is not None else None
+            P, Pd = None, ops.attn_fwd_hd(qkv, o, lse, B, N, H, D // H, scale, p_attn, seeds[0], mask=pm)
+        elif flash:
             o = torch.empty(M, D, dtype=c, device=dev)
             lse = torch.empty(B, H, N, dtype=F32, device=dev)
             pm = premask[1] if premask is not None else None
@@ -430,7 +439,12 @@ class BlockFn(torch.autograd.Function):
         do = torch.empty(M, D, dtype=c, device=dev)
         linear_dx_w(dprep, projw, do)
         del dprep
-        if flash:
+        if flash and D // H != 64:
+            dqkv = torch.empty(M, 3 * D, dtype=c, device=dev)
+            dvec = torch.empty(B, H, N, dtype=F32, device=dev)
+            ops.attn_bwd_hd(qkv, o, do, lse, dvec, dqkv, B, N, H, D // H, scale, p_attn, seeds[0], mask=Pd,
+                            dbias=grad_buf(qkvb) if RT.attn_bias_grad else None)
+        elif flash:
             dqkv = torch.empty(M, 3 * D, dtype=c, device=dev)
             dvec = torch.empty(B, H, N, dtype=F32, device=dev)
             # the qkv bias gradient comes out of the attention backward's epilogues (column partials of dqkv)

@@ -556,6 +556,49 @@ def attn_bwd(qkv, out, dout, lse2, dvec, dqkv, B, N, H, scale, drop_p=0.0, seed=
                    ptr(dvec), ptr(dqkv), ptr(ws), B, N, H, float(scale), float(drop_p), stream())
 
 
+def attn_hd_supported(head_dim):
+    """does the fused attention of csrc/attention_hd.hip serve this head_dim (80, 128)?  64 is attn_fwd's."""
+    return bool(lib().query("uva_attn_hd_supported", int(head_dim)))
+
+
+def attn_fwd_hd(qkv, out, lse2, B, N, H, head_dim, scale, drop_p=0.0, seed=0, mask=None):
+    """attn_fwd at head_dim 80 / 128 -> the dropout mask planes (None when drop_p == 0); pass them to
+    attn_bwd_hd.  The planes are attn_dropmask's: they do not depend on head_dim."""
+    hd = int(head_dim)
+    assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and out.is_contiguous()
+    assert attn_hd_supported(hd), f"head_dim {hd}: the fused kernels serve 80 and 128 (64: attn_fwd)"
+    assert N % 64 == 0 and qkv.shape[-1] == 3 * H * hd
+    assert qkv.numel() == B * N * 3 * H * hd and out.numel() == B * N * H * hd and lse2.numel() == B * H * N
+    with _traced(f"attn_fwd_hd{hd} B{B} N{N} H{H}", 4.0 * B * H * N * N * hd):
+        if drop_p > 0 and mask is None:
+            mask = attn_dropmask(B, N, H, drop_p, seed, qkv.device)
+        _call("uva_attn_fwd_hd", ptr(qkv), ptr(out), ptr(lse2), ptr(mask) if drop_p > 0 else None, B, N, H, hd,
+              float(scale), float(drop_p), stream())
+    return mask if drop_p > 0 else None
+
+
+def attn_bwd_hd(qkv, out, dout, lse2, dvec, dqkv, B, N, H, head_dim, scale, drop_p=0.0, seed=0, mask=None,
+                dbias=None, accum_bias=True):
+    """attn_bwd at head_dim 80 / 128 -> dqkv; with `dbias` ([3 H head_dim] fp32) also the qkv bias gradient
+    (column sums of dqkv as stored) from the kernels' epilogues"""
+    hd = int(head_dim)
+    assert dout.dtype == torch.bfloat16 and dout.is_contiguous() and dqkv.is_contiguous()
+    assert attn_hd_supported(hd), f"head_dim {hd}: the fused kernels serve 80 and 128 (64: attn_bwd)"
+    assert N % 64 == 0 and qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and out.is_contiguous()
+    assert dout.numel() == B * N * H * hd and dqkv.numel() == B * N * 3 * H * hd and dvec.numel() == B * H * N
+    assert qkv.numel() == dqkv.numel() and out.numel() == dout.numel() and lse2.numel() == B * H * N
+    with _traced(f"attn_bwd_hd{hd} B{B} N{N} H{H}", 8.0 * B * H * N * N * hd):
+        if drop_p > 0 and mask is None:
+            mask = attn_dropmask(B, N, H, drop_p, seed, qkv.device)
+        ws = None
+        if dbias is not None:
+            assert dbias.dtype == torch.float32 and dbias.numel() == 3 * H * hd and dbias.is_contiguous()
+            ws = workspace(lib().query("uva_attn_bwd_hd_part_floats", B, N, H, hd), qkv.device)
+        _call("uva_attn_bwd_hd", ptr(qkv), ptr(out), ptr(dout), ptr(lse2), ptr(mask) if drop_p > 0 else None,
+              ptr(dvec), ptr(dqkv), ptr(dbias), int(accum_bias), ptr(ws), B, N, H, hd, float(scale), float(drop_p),
+              stream())
+
+
 def conv2d(x, w, out, Nimg, Hin, Win, Ci, Co, ks, stride, pad_t, pad_l, Hout, Wout, bias=None, residual=None,
            gn_scale=None, gn_shift=None, gn_silu=True, act="none", force_generic=False, gn_part=None):
     """NHWC implicit-GEMM conv; w stored [Co][ks][ks][Ci]."""

@@ -18,6 +18,9 @@ without a GPU) and for op-level parity tests (tests/test_torch_ops_cpu.py, tests
   uva::attention(qkv, heads, drop_p, seed) -> (out, lse)
       F.scaled_dot_product_attention of timm Attention (mar_con_unified.py:201-215): qkv [B, N, 3*H*64]
       bf16 as the qkv Linear writes it, out [B, N, H*64], lse [B, H, N] (base-2 log-sum-exp).
+  uva::attention_hd(qkv, heads, head_dim, drop_p, seed) -> (out, lse)
+      the same at head_dim 80 (mar_huge) and 128 (mar_tiny / mar_small): qkv [B, N, 3*H*head_dim];
+      backward uva::attention_hd_backward.
   uva::conv3x3(x, weight, bias?, gn_scale?, gn_shift?, residual?) -> y
       KL-VAE ResnetBlock conv over NHWC bf16 with the GroupNorm-apply + SiLU prologue and the residual
       add fused (vaekl.py:56-113); forward only (the VAE is frozen on the training path).
@@ -232,6 +235,72 @@ def _attn_backward(ctx, dout, _dlse):
 
 
 attention.register_autograd(_attn_backward, setup_context=_attn_setup)
+
+
+# ---- attention at head_dim 80 / 128 ------------------------------------------------------------
+_HD_DIMS = (80, 128)
+
+
+def _attn_hd_dims(qkv: Tensor, heads: int, head_dim: int):
+    if head_dim not in _HD_DIMS:
+        raise ValueError(f"uva::attention_hd: head_dim must be one of {_HD_DIMS} (64: uva::attention), got {head_dim}")
+    if qkv.dim() != 3 or qkv.shape[-1] != 3 * heads * head_dim:
+        raise ValueError(f"uva::attention_hd: qkv must be [B, N, 3*heads*{head_dim}], got {tuple(qkv.shape)} "
+                         f"for {heads} heads")
+    B, N = qkv.shape[0], qkv.shape[1]
+    if N % 64:
+        raise ValueError(f"uva::attention_hd: N = {N} must be a multiple of 64")
+    return B, N
+
+
+@torch.library.custom_op("uva::attention_hd", mutates_args=(), device_types="cuda")
+def attention_hd(qkv: Tensor, heads: int, head_dim: int, drop_p: float, seed: int) -> Tuple[Tensor, Tensor]:
+    B, N = _attn_hd_dims(qkv, heads, head_dim)
+    q = qkv.to(torch.bfloat16).contiguous()
+    out = torch.empty(B, N, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
+    lse = torch.empty(B, heads, N, dtype=F32, device=qkv.device)
+    ops.attn_fwd_hd(q, out, lse, B, N, heads, head_dim, head_dim ** -0.5, drop_p=drop_p, seed=seed)
+    return out, lse
+
+
+@attention_hd.register_fake
+def _attention_hd_fake(qkv, heads, head_dim, drop_p, seed):
+    B, N = _attn_hd_dims(qkv, heads, head_dim)
+    return qkv.new_empty(B, N, heads * head_dim, dtype=torch.bfloat16), qkv.new_empty(B, heads, N, dtype=F32)
+
+
+@torch.library.custom_op("uva::attention_hd_backward", mutates_args=(), device_types="cuda")
+def attention_hd_backward(dout: Tensor, qkv: Tensor, out: Tensor, lse: Tensor, heads: int, head_dim: int,
+                          drop_p: float, seed: int) -> Tensor:
+    B, N = _attn_hd_dims(qkv, heads, head_dim)
+    q = qkv.to(torch.bfloat16).contiguous()
+    dqkv = torch.empty(q.shape, dtype=torch.bfloat16, device=qkv.device)
+    dvec = torch.empty(B, heads, N, dtype=F32, device=qkv.device)
+    ops.attn_bwd_hd(q, out.contiguous(), dout.to(torch.bfloat16).contiguous(), lse, dvec, dqkv, B, N, heads,
+                    head_dim, head_dim ** -0.5, drop_p=drop_p, seed=seed)
+    return dqkv.to(qkv.dtype)
+
+
+@attention_hd_backward.register_fake
+def _attention_hd_backward_fake(dout, qkv, out, lse, heads, head_dim, drop_p, seed):
+    _attn_hd_dims(qkv, heads, head_dim)
+    return torch.empty_like(qkv)
+
+
+def _attn_hd_setup(ctx, inputs, output):
+    qkv, heads, head_dim, drop_p, seed = inputs
+    out, lse = output
+    ctx.save_for_backward(qkv, out, lse)
+    ctx.cfg = (heads, head_dim, drop_p, seed)
+
+
+def _attn_hd_backward(ctx, dout, _dlse):
+    qkv, out, lse = ctx.saved_tensors
+    heads, head_dim, drop_p, seed = ctx.cfg
+    return attention_hd_backward(dout, qkv, out, lse, heads, head_dim, drop_p, seed), None, None, None, None
+
+
+attention_hd.register_autograd(_attn_hd_backward, setup_context=_attn_hd_setup)
 
 
 # ---- VAE 3x3 convolution (forward only) --------------------------------------------------------
