@@ -91,7 +91,7 @@ def plane_words(seed64, n, thresh):
 
 
 def mask_pos(k):
-    """position of element k (0..63) of a 64-wide tile inside an MQ / MK word (attention.hip mask_pos)"""
+    """position of element k (0..63) of a 64-wide tile inside an MQ / MK word (attention_frag.h mask_pos)"""
     return ((k >> 2) & 3) * 16 + (k >> 4) * 4 + (k & 3)
 
 

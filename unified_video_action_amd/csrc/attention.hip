@@ -32,30 +32,15 @@
 // The dropout scale dsc = 1 / (1 - p) never enters the loops: they run on the unscaled dO with
 // D' = rowsum(dO * O) / dsc formed by the dQ kernel, which runs first (dS = dsc P (keep dP - D')), and dsc multiplies dK,
 // dQ and dV once when they are stored.
-#include "common.h"
+#include "attention_frag.h"
 
-#ifndef UVA_ATT_PIPE
-#define UVA_ATT_PIPE 0
-#endif
-#ifndef UVA_ATT_PIPE_DQ
-#define UVA_ATT_PIPE_DQ 0
-#endif
-// UVA_ATT_PRIO: s_setprio(1) around the MFMA blocks, so that on a SIMD the wave in its matrix phase
+// s_setprio(1) around the forward's MFMA blocks, so that on a SIMD the wave in its matrix phase
 // wins the issue slots over the co-resident wave's softmax / staging phase (the GN conv measured
-// 37 % slower without its equivalent)
-// forward: on (0.162-0.168 vs 0.166-0.171 ms at B32/N1024/H12); backward: off (p = 0.1: 0.70 vs
-// 0.49 ms -- the barrier the builtin puts in hipcc's schedule splits the dropout-bit / softmax
-// interleave), profiles/r04/ab_attn_setprio.txt
-#ifndef UVA_ATT_PRIO
-#define UVA_ATT_PRIO 1
-#endif
-#ifndef UVA_ATT_PRIO_BWD
-#define UVA_ATT_PRIO_BWD 0
-#endif
-#define ATT_PRIO_HI() do { if (UVA_ATT_PRIO) __builtin_amdgcn_s_setprio(1); } while (0)
-#define ATT_PRIO_LO() do { if (UVA_ATT_PRIO) __builtin_amdgcn_s_setprio(0); } while (0)
-#define ATT_PRIO_HI_BWD() do { if (UVA_ATT_PRIO_BWD) __builtin_amdgcn_s_setprio(1); } while (0)
-#define ATT_PRIO_LO_BWD() do { if (UVA_ATT_PRIO_BWD) __builtin_amdgcn_s_setprio(0); } while (0)
+// 37 % slower without its equivalent): 0.162-0.168 vs 0.166-0.171 ms at B32/N1024/H12.  The backward
+// kernels run without it (p = 0.1: 0.70 vs 0.49 ms -- the barrier the builtin puts in hipcc's
+// schedule splits the dropout-bit / softmax interleave), profiles/r04/ab_attn_setprio.txt
+#define ATT_PRIO_HI() __builtin_amdgcn_s_setprio(1)
+#define ATT_PRIO_LO() __builtin_amdgcn_s_setprio(0)
 // 64 x 64 bf16 tile images with 160-B rows (80 elements).  Under gfx950's LDS lane groups
 // (MI355X_MICROARCH.md 'LDS banking': ds_read_b128 in 4 x 16 lanes {0-3,12-15,20-27} ...,
 // ds_read_b64_tr_b16 in 2 x 32) both fragment reads below are conflict-free
@@ -67,45 +52,10 @@
 #define AT_LD 80
 #define AT_TILE (64 * AT_LD)
 
-__device__ __forceinline__ bf16x8 lds_row_frag(const bf16* lds, int row0, int ks) {
-  const int l = threadIdx.x & 63;
-  return *(const bf16x8*)(lds + (row0 + (l & 15)) * AT_LD + ks * 32 + 8 * (l >> 4));
-}
-
-__device__ __forceinline__ bf16x8 lds_tr_frag(const bf16* lds, int rowA, int rowB, int col0) {
-  const int l = threadIdx.x & 63, g = l >> 4, q = (l >> 2) & 3, p = l & 3;
-  const bf16* a0 = lds + (rowA + 4 * g + q) * AT_LD + col0 + 4 * p;
-  const bf16* a1 = lds + (rowB + 4 * g + q) * AT_LD + col0 + 4 * p;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a0));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a1));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// two f32 -> one dword of two bf16 (RNE, as the (bf16) cast): one v_cvt_pk_bf16_f32 per pair.  Plain
-// casts of individually masked values compiled to one cvt per element + a v_perm per pair.
-// (a vector conversion, not inline asm: the result feeds MFMAs, whose operand hazards hipcc only
-// tracks for instructions it emitted itself)
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){lo, hi}, bf16x2));
-}
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-__device__ __forceinline__ bf16x8 pack_pi(const f32x4& a, const f32x4& b) {
-  const u32x4 u = {cvt_pk_bf16(a[0], a[1]), cvt_pk_bf16(a[2], a[3]), cvt_pk_bf16(b[0], b[1]), cvt_pk_bf16(b[2], b[3])};
-  return __builtin_bit_cast(bf16x8, u);
-}
-
-__device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 // 64 rows x 64 cols of a strided bf16 matrix -> 2 chunks (16 B) per thread.  Tiles are always
 // full (N % 64 == 0 is an ABI precondition), so no per-row guard (its exec-mask branches
 // serialised the loads); the uniform tile base is formed once, per-thread offsets are hoisted.
-__device__ __forceinline__ void stage_load(const bf16* __restrict__ g, long long ld, int row0, int nrows,
-                                           bf16x8 (&r)[2]) {
-  (void)nrows;
+__device__ __forceinline__ void stage_load(const bf16* __restrict__ g, long long ld, int row0, bf16x8 (&r)[2]) {
   const int t = threadIdx.x;
   const bf16* base = g + (long long)row0 * ld;
 #pragma unroll
@@ -123,15 +73,8 @@ __device__ __forceinline__ void stage_store(bf16* lds, const bf16x8 (&r)[2]) {
   }
 }
 
-__device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
-// keep-bit b of a mask word as an all-ones / all-zeros 32-bit mask.  (A v_bfe_i32 in inline asm
-// saves hipcc's v_and + v_cmp + v_cndmask lowering but measured slower in the dK/dV loop: the
-// asm statements constrain its scheduling.)
-__device__ __forceinline__ float keep_and(float v, uint32_t w, int b) {
-  return __int_as_float(__float_as_int(v) & __builtin_amdgcn_sbfe(w, b, 1));
-}
-// the same as two instructions (v_bfe_i32 + v_and_b32): from the builtin form hipcc derives a bit test
-// + v_cmp + v_cndmask (three) in the forward and dQ loops
+// keep_bit (attention_frag.h) as two instructions (v_bfe_i32 + v_and_b32): from the builtin form hipcc
+// derives a bit test + v_cmp + v_cndmask (three) in the forward and dQ loops
 __device__ __forceinline__ float keep_bfe(float v, uint32_t w, int b) {
   int m;
   asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(w), "s"(b));
@@ -140,17 +83,6 @@ __device__ __forceinline__ float keep_bfe(float v, uint32_t w, int b) {
 // max of two MFMA outputs without the canonicalising v_max hipcc inserts in front of fmaxf
 // (med3(a, b, +inf) == max(a, b); the compiler fuses chains of it into v_max3_f32)
 __device__ __forceinline__ float fmax_nc(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, INFINITY); }
-// max over lanes l, l^16, l^32, l^48 by v_permlane16/32_swap (VALU) instead of two ds_bpermute.
-// Builtins only: an inline-asm producer is invisible to hipcc's permlane / trans / MFMA hazard
-// wait-state insertion (an asm v_max feeding the second swap read a stale register).
-__device__ __forceinline__ float quad_max(float v) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-  r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-// position of element k (0..63) of a 64-wide tile inside an MQ / MK word (an involution)
-__host__ __device__ constexpr int mask_pos(int k) { return ((k >> 2) & 3) * 16 + (k >> 4) * 4 + (k & 3); }
 
 // =====================================================================================
 // dropout bit planes: one wave per (bh, query tile qb, MASK_TPW consecutive key tiles)
@@ -282,8 +214,8 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const bf16* __restri
   bf16x8 rk[NH][2], rv[NH][2];
 #pragma unroll
   for (int hh = 0; hh < NH; ++hh) {
-    stage_load(Kg, ld, hh * 64, N, rk[hh]);
-    stage_load(Vg, ld, hh * 64, N, rv[hh]);
+    stage_load(Kg, ld, hh * 64, rk[hh]);
+    stage_load(Vg, ld, hh * 64, rv[hh]);
   }
 #pragma unroll
   for (int hh = 0; hh < NH; ++hh) {
@@ -297,8 +229,8 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const bf16* __restri
     if (more) {
 #pragma unroll
       for (int hh = 0; hh < NH; ++hh) {
-        stage_load(Kg, ld, (kv + 1) * KT + hh * 64, N, rk[hh]);
-        stage_load(Vg, ld, (kv + 1) * KT + hh * 64, N, rv[hh]);
+        stage_load(Kg, ld, (kv + 1) * KT + hh * 64, rk[hh]);
+        stage_load(Vg, ld, (kv + 1) * KT + hh * 64, rv[hh]);
       }
       if (DROP) {
 #pragma unroll
@@ -322,7 +254,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const bf16* __restri
     for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt) {
-        const bf16x8 kf = lds_row_frag(cK, kt * 16, ks);
+        const bf16x8 kf = row_frag<AT_LD>(cK, kt * 16, ks);
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) s[kt][qt] = mfma16(kf, qf[qt][ks], s[kt][qt]);
       }
@@ -379,7 +311,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const bf16* __restri
       for (int qt = 0; qt < 2; ++qt) pf[qt] = pack_pi(s[2 * ks][qt], s[2 * ks + 1][qt]);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        const bf16x8 vf = lds_tr_frag(cV, 32 * ks, 32 * ks + 16, dt * 16);
+        const bf16x8 vf = tr_frag<AT_LD>(cV, 32 * ks, 32 * ks + 16, dt * 16);
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) o[qt][dt] = mfma16(vf, pf[qt], o[qt][dt]);
       }
@@ -472,8 +404,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16* __res
     for (int kt = 0; kt < 2; ++kt) dv[dt][kt] = dk[dt][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   bf16x8 rq[2], ro[2];
-  stage_load(Qg, ld, 0, N, rq);
-  stage_load(dOg, ldo, 0, N, ro);
+  stage_load(Qg, ld, 0, rq);
+  stage_load(dOg, ldo, 0, ro);
   stage_store(sQ[0], rq);
   stage_store(sO[0], ro);
   if (threadIdx.x < 64) { sL[0][threadIdx.x] = Lg[threadIdx.x]; sD[0][threadIdx.x] = Dg[threadIdx.x]; }
@@ -483,8 +415,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16* __res
     const bool more = qi + 1 < nq;
     float nl = 0.f, nd = 0.f;
     if (more) {
-      stage_load(Qg, ld, (qi + 1) * 64, N, rq);
-      stage_load(dOg, ldo, (qi + 1) * 64, N, ro);
+      stage_load(Qg, ld, (qi + 1) * 64, rq);
+      stage_load(dOg, ldo, (qi + 1) * 64, ro);
       if (threadIdx.x < 64) { nl = Lg[(qi + 1) * 64 + threadIdx.x]; nd = Dg[(qi + 1) * 64 + threadIdx.x]; }
       if (DROP) {
 #pragma unroll
@@ -500,97 +432,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16* __res
     for (int qt = 0; qt < 4; ++qt)
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) s[qt][kt] = dp[qt][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#if UVA_ATT_PIPE
-    // software-pipelined form: the tile is walked in query halves so that every MFMA run has
-    // independent VALU beside it -- S / dP of queries 32..63 beside the softmax of 0..31, dV / dK of
-    // 0..31 beside the softmax of 32..63 (hipcc otherwise issues the 32 S / dP MFMAs, then all the
-    // softmax VALU, then the 32 dV / dK MFMAs: each wave alternates matrix-only and vector-only runs)
-    auto sdp = [&](int qt) __attribute__((always_inline)) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 a = lds_row_frag(sQ[cur], qt * 16, ks);
-        const bf16x8 e = lds_row_frag(sO[cur], qt * 16, ks);
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-          s[qt][kt] = mfma16(a, kf[kt][ks], s[qt][kt]);
-          dp[qt][kt] = mfma16(e, vf[kt][ks], dp[qt][kt]);
-        }
-      }
-    };
-    auto soft = [&](int qt) __attribute__((always_inline)) {
-      const f32x4 Lq = *(const f32x4*)&sL[cur][qt * 16 + 4 * g];
-      const f32x4 Dq = *(const f32x4*)&sD[cur][qt * 16 + 4 * g];
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-          const float p = exp2_fast(fmaf(s[qt][kt][r], c, -Lq[r]));
-          if (DROP) {
-            const float pd = keep_bfe(p, mw[kt], qt * 4 + r);
-            s[qt][kt][r] = pd;
-            dp[qt][kt][r] = fmaf(pd, dp[qt][kt][r], -(p * Dq[r]));
-          } else {
-            s[qt][kt][r] = p;
-            dp[qt][kt][r] = p * (dp[qt][kt][r] - Dq[r]);
-          }
-        }
-    };
-    auto dkdv = [&](int ks) __attribute__((always_inline)) {
-      bf16x8 pb[2], sb[2];
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) {
-        pb[kt] = pack_pi(s[2 * ks][kt], s[2 * ks + 1][kt]);
-        sb[kt] = pack_pi(dp[2 * ks][kt], dp[2 * ks + 1][kt]);
-      }
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const bf16x8 oa = lds_tr_frag(sO[cur], 32 * ks, 32 * ks + 16, dt * 16);
-        const bf16x8 qa = lds_tr_frag(sQ[cur], 32 * ks, 32 * ks + 16, dt * 16);
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-          dv[dt][kt] = mfma16(oa, pb[kt], dv[dt][kt]);
-          dk[dt][kt] = mfma16(qa, sb[kt], dk[dt][kt]);
-        }
-      }
-    };
-    sdp(0);
-    sdp(1);
-    __builtin_amdgcn_sched_barrier(0);
-    sdp(2);
-    sdp(3);
-    soft(0);
-    soft(1);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);  // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x002, 6, 1);  // VALU
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    dkdv(0);
-    soft(2);
-    soft(3);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 2);
-      __builtin_amdgcn_sched_group_barrier(0x002, 6, 2);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    dkdv(1);
-#else
-    ATT_PRIO_HI_BWD();
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int qt = 0; qt < 4; ++qt) {
-        bf16x8 a = lds_row_frag(sQ[cur], qt * 16, ks);
-        bf16x8 e = lds_row_frag(sO[cur], qt * 16, ks);
+        bf16x8 a = row_frag<AT_LD>(sQ[cur], qt * 16, ks);
+        bf16x8 e = row_frag<AT_LD>(sO[cur], qt * 16, ks);
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
           s[qt][kt] = mfma16(a, kf[kt][ks], s[qt][kt]);
           dp[qt][kt] = mfma16(e, vf[kt][ks], dp[qt][kt]);
         }
       }
-    ATT_PRIO_LO_BWD();
     // P = exp2(S c - L);  Pd = keep P;  dS = P (keep dP' - D)      (s <- Pd, dp <- dS)
 #pragma unroll
     for (int qt = 0; qt < 4; ++qt) {
@@ -613,7 +466,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16* __res
         }
     }
     // dV^T[d][key] += dO'^T Pd ; dK^T[d][key] += Q^T dS      (k = q, permuted by pi)
-    ATT_PRIO_HI_BWD();
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 pb[2], sb[2];
@@ -624,8 +476,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16* __res
       }
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        bf16x8 oa = lds_tr_frag(sO[cur], 32 * ks, 32 * ks + 16, dt * 16);
-        bf16x8 qa = lds_tr_frag(sQ[cur], 32 * ks, 32 * ks + 16, dt * 16);
+        bf16x8 oa = tr_frag<AT_LD>(sO[cur], 32 * ks, 32 * ks + 16, dt * 16);
+        bf16x8 qa = tr_frag<AT_LD>(sQ[cur], 32 * ks, 32 * ks + 16, dt * 16);
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
           dv[dt][kt] = mfma16(oa, pb[kt], dv[dt][kt]);
@@ -633,8 +485,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16* __res
         }
       }
     }
-    ATT_PRIO_LO_BWD();
-#endif
     if (more) {
       stage_store(sQ[cur ^ 1], rq);
       stage_store(sO[cur ^ 1], ro);
@@ -697,16 +547,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16* __res
 // backward dQ (block = 4 waves x 32 queries, sweeps all 64-key tiles; transposed lane view as
 // in the forward: q = qt*16 + li, key = kt*16 + 4g + r)
 //   S^T = K Q^T, dP'^T = V dO'^T, dQ^T[d][q] += K^T dS^T  (dS^T packed in pi order as the B operand)
-// =====================================================================================
-template <bool DROP>
-#ifndef UVA_ATT_DQ_OCC
-#define UVA_ATT_DQ_OCC 2
-#endif
 // D' = dmul * rowsum(dO * O) is formed here for the block's own queries (the lanes of a query hold
 // its 64 dO / O values in four 16-element runs: two permlane-free shuffles) and written to Dvec for the
 // dK / dV kernel that runs after this one: no separate prologue pass (its 2 x 25 MB per layer of dO / O
 // reads and launch), O read once more here instead.
-__global__ __launch_bounds__(256, UVA_ATT_DQ_OCC) void attn_bwd_dq_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ dOs,
+// =====================================================================================
+template <bool DROP>
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16* __restrict__ qkv,
+                                                             const bf16* __restrict__ dOs,
                                                              const bf16* __restrict__ Os,
                                                              const float* __restrict__ lse2,
                                                              float* __restrict__ Dvec,
@@ -759,8 +607,8 @@ __global__ __launch_bounds__(256, UVA_ATT_DQ_OCC) void attn_bwd_dq_kernel(const 
     for (int qt = 0; qt < 2; ++qt) dq[dt][qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   bf16x8 rk[2], rv[2];
-  stage_load(Kg, ld, 0, N, rk);
-  stage_load(Vg, ld, 0, N, rv);
+  stage_load(Kg, ld, 0, rk);
+  stage_load(Vg, ld, 0, rv);
   stage_store(sK[0], rk);
   stage_store(sV[0], rv);
   __syncthreads();
@@ -768,8 +616,8 @@ __global__ __launch_bounds__(256, UVA_ATT_DQ_OCC) void attn_bwd_dq_kernel(const 
   for (int kv = 0; kv < nkv; ++kv) {
     const bool more = kv + 1 < nkv;
     if (more) {
-      stage_load(Kg, ld, (kv + 1) * 64, N, rk);
-      stage_load(Vg, ld, (kv + 1) * 64, N, rv);
+      stage_load(Kg, ld, (kv + 1) * 64, rk);
+      stage_load(Vg, ld, (kv + 1) * 64, rv);
       if (DROP) {
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
@@ -783,81 +631,18 @@ __global__ __launch_bounds__(256, UVA_ATT_DQ_OCC) void attn_bwd_dq_kernel(const 
     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) s[kt][qt] = dp[kt][qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#if UVA_ATT_PIPE_DQ
-    // software-pipelined in key halves (as dK / dV): S / dP of keys 32..63 beside the softmax of keys
-    // 0..31, dQ of keys 0..31 beside the softmax of 32..63
-    auto sdp = [&](int kt) __attribute__((always_inline)) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 ka = lds_row_frag(sK[cur], kt * 16, ks);
-        const bf16x8 va = lds_row_frag(sV[cur], kt * 16, ks);
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-          s[kt][qt] = mfma16(ka, qf[qt][ks], s[kt][qt]);
-          dp[kt][qt] = mfma16(va, of[qt][ks], dp[kt][qt]);
-        }
-      }
-    };
-    auto soft = [&](int kt) __attribute__((always_inline)) {
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = exp2_fast(fmaf(s[kt][qt][r], c, -L[qt]));
-          float dpt = dp[kt][qt][r];
-          if (DROP) dpt = keep_bfe(dpt, mw[qt], kt * 4 + r);
-          s[kt][qt][r] = p * (dpt - Dq[qt]);
-        }
-    };
-    auto dqk = [&](int ks) __attribute__((always_inline)) {
-      bf16x8 sb[2];
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) sb[qt] = pack_pi(s[2 * ks][qt], s[2 * ks + 1][qt]);
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const bf16x8 ka = lds_tr_frag(sK[cur], 32 * ks, 32 * ks + 16, dt * 16);
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) dq[dt][qt] = mfma16(ka, sb[qt], dq[dt][qt]);
-      }
-    };
-    sdp(0);
-    sdp(1);
-    __builtin_amdgcn_sched_barrier(0);
-    sdp(2);
-    sdp(3);
-    soft(0);
-    soft(1);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-      __builtin_amdgcn_sched_group_barrier(0x002, 5, 1);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    dqk(0);
-    soft(2);
-    soft(3);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 2);
-      __builtin_amdgcn_sched_group_barrier(0x002, 10, 2);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    dqk(1);
-#else
-    ATT_PRIO_HI_BWD();
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) {
-        const bf16x8 ka = lds_row_frag(sK[cur], kt * 16, ks);
-        const bf16x8 va = lds_row_frag(sV[cur], kt * 16, ks);
+        const bf16x8 ka = row_frag<AT_LD>(sK[cur], kt * 16, ks);
+        const bf16x8 va = row_frag<AT_LD>(sV[cur], kt * 16, ks);
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
           s[kt][qt] = mfma16(ka, qf[qt][ks], s[kt][qt]);
           dp[kt][qt] = mfma16(va, of[qt][ks], dp[kt][qt]);
         }
       }
-    ATT_PRIO_LO_BWD();
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
@@ -869,7 +654,6 @@ __global__ __launch_bounds__(256, UVA_ATT_DQ_OCC) void attn_bwd_dq_kernel(const 
           if (DROP) dpt = keep_bfe(dpt, mw[qt], kt * 4 + r);
           s[kt][qt][r] = p * (dpt - Dq[qt]);
         }
-    ATT_PRIO_HI_BWD();
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 sb[2];
@@ -877,13 +661,11 @@ __global__ __launch_bounds__(256, UVA_ATT_DQ_OCC) void attn_bwd_dq_kernel(const 
       for (int qt = 0; qt < 2; ++qt) sb[qt] = pack_pi(s[2 * ks][qt], s[2 * ks + 1][qt]);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        const bf16x8 ka = lds_tr_frag(sK[cur], 32 * ks, 32 * ks + 16, dt * 16);
+        const bf16x8 ka = tr_frag<AT_LD>(sK[cur], 32 * ks, 32 * ks + 16, dt * 16);
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) dq[dt][qt] = mfma16(ka, sb[qt], dq[dt][qt]);
       }
     }
-    ATT_PRIO_LO_BWD();
-#endif
     if (more) {
       stage_store(sK[cur ^ 1], rk);
       stage_store(sV[cur ^ 1], rv);
@@ -978,30 +760,6 @@ extern "C" int uva_attn_fwd(const void* qkv, void* out, float* lse2, const void*
 
 static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse2, const void* mask,
                            float* Dvec, void* dqkv, int B, int N, int H, float scale, float drop_p, float* cpart,
-                           hipStream_t s);
-
-extern "C" int uva_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse2, const void* mask,
-                            float* Dvec, void* dqkv, void* workspace, int B, int N, int H, float scale, float drop_p,
-                            hipStream_t s) {
-  (void)workspace;
-  return attn_bwd_launch(qkv, out, dout, lse2, mask, Dvec, dqkv, B, N, H, scale, drop_p, nullptr, s);
-}
-
-int uva_colsum_final_launch(const float* part, int nrows, int cols, float* out, int accum, hipStream_t s);
-
-// + the qkv Linear's bias gradient (the column sums of dqkv as stored): per-(batch, 128-row block) partials
-// written by the two kernels' epilogues into `part` ((B * ceil(N / 128)) * 3 H 64 floats), reduced into dbias
-extern "C" int uva_attn_bwd_bias(const void* qkv, const void* out, const void* dout, const float* lse2,
-                                 const void* mask, float* Dvec, void* dqkv, float* dbias, int accum, float* part, int B,
-                                 int N, int H, float scale, float drop_p, hipStream_t s) {
-  if (!dbias || !part) return (int)hipErrorInvalidValue;
-  int r = attn_bwd_launch(qkv, out, dout, lse2, mask, Dvec, dqkv, B, N, H, scale, drop_p, part, s);
-  if (r) return r;
-  return uva_colsum_final_launch(part, B * ((N + 127) / 128), 3 * H * 64, dbias, accum, s);
-}
-
-static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse2, const void* mask,
-                           float* Dvec, void* dqkv, int B, int N, int H, float scale, float drop_p, float* cpart,
                            hipStream_t s) {
   if (N % 64 != 0) return (int)hipErrorInvalidValue;
   const bool drop = drop_p > 0.f;
@@ -1009,11 +767,9 @@ static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, c
   uint32_t th;
   float ds;
   uva_drop_params(drop_p, &th, &ds);
-  const long long rows = (long long)B * N * H;
   // the dropout scale 1/(1-p) is not applied to dO: dP' = dsc dO V^T, so dS = dsc P (keep dP - D / dsc),
   // i.e. the loops run on the unscaled dO with D' = D / dsc, and dsc goes on dK, dQ, dV once at the
   // end (no scaled dO copy: one [B N H 64] bf16 write + its re-reads per layer saved)
-  (void)rows;
   const int nt = N / 64;
   const uint64_t* MQ = (const uint64_t*)mask;
   const uint64_t* MK = drop ? MQ + (long long)B * H * N * nt : nullptr;
@@ -1036,4 +792,24 @@ static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, c
   }
   UVA_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int uva_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse2, const void* mask,
+                            float* Dvec, void* dqkv, void* workspace, int B, int N, int H, float scale, float drop_p,
+                            hipStream_t s) {
+  (void)workspace;
+  return attn_bwd_launch(qkv, out, dout, lse2, mask, Dvec, dqkv, B, N, H, scale, drop_p, nullptr, s);
+}
+
+int uva_colsum_final_launch(const float* part, int nrows, int cols, float* out, int accum, hipStream_t s);
+
+// + the qkv Linear's bias gradient (the column sums of dqkv as stored): per-(batch, 128-row block) partials
+// written by the two kernels' epilogues into `part` ((B * ceil(N / 128)) * 3 H 64 floats), reduced into dbias
+extern "C" int uva_attn_bwd_bias(const void* qkv, const void* out, const void* dout, const float* lse2,
+                                 const void* mask, float* Dvec, void* dqkv, float* dbias, int accum, float* part, int B,
+                                 int N, int H, float scale, float drop_p, hipStream_t s) {
+  if (!dbias || !part) return (int)hipErrorInvalidValue;
+  int r = attn_bwd_launch(qkv, out, dout, lse2, mask, Dvec, dqkv, B, N, H, scale, drop_p, part, s);
+  if (r) return r;
+  return uva_colsum_final_launch(part, B * ((N + 127) / 128), 3 * H * 64, dbias, accum, s);
 }

@@ -1,8 +1,8 @@
 // Fused multi-head attention at head_dim 80 and 128 (non-causal, bf16 in/out, fp32 online softmax)
 // for the mar_huge (D 1280, 16 heads) and mar_tiny / mar_small (D 768, 6 heads) presets of
 // mar_con_unified.py:201-249 (timm Attention = SDPA with dropout_p = attn_drop while training).
-// The design is attention.hip's (head_dim 64), restated with the head width as a template
-// parameter; that file's kernels are not touched and nothing here is tuned:
+// The design is attention.hip's (head_dim 64) with the head width as a template parameter, on the
+// device helpers both files share (attention_frag.h); nothing here is tuned:
 //   * S^T = K Q^T with the query on the lane, P^T packed in the pi order as the B operand of
 //     O^T = V^T P^T (v_mfma_f32_16x16x32_bf16, V through ds_read_b64_tr_b16), lazy rescale;
 //   * Q/K/V read straight from the qkv GEMM output [B, N, 3, H, HD], O written as [B, N, H, HD],
@@ -35,54 +35,13 @@
 // x 16 rows of the 128-row block), __launch_bounds__(512): 256 VGPRs, one workgroup per CU (two waves
 // per SIMD): at 32 rows per wave the dK / dV kernel's accumulators (2 x 16 x HD / 64 registers), its
 // K / V rows and the S / dP tiles do not fit 256 registers at head_dim 128.
-#include "common.h"
+#include "attention_frag.h"
 
 namespace {
 
 template <int HD> struct HdCfg;
 template <> struct HdCfg<80> { static constexpr int KS = 3, DT = 5, LD = 112; };
 template <> struct HdCfg<128> { static constexpr int KS = 4, DT = 8, LD = 144; };
-
-template <int LD>
-__device__ __forceinline__ bf16x8 row_frag(const bf16* lds, int row0, int ks) {
-  const int l = threadIdx.x & 63;
-  return *(const bf16x8*)(lds + (row0 + (l & 15)) * LD + ks * 32 + 8 * (l >> 4));
-}
-
-template <int LD>
-__device__ __forceinline__ bf16x8 tr_frag(const bf16* lds, int rowA, int rowB, int col0) {
-  const int l = threadIdx.x & 63, g = l >> 4, q = (l >> 2) & 3, p = l & 3;
-  const bf16* a0 = lds + (rowA + 4 * g + q) * LD + col0 + 4 * p;
-  const bf16* a1 = lds + (rowB + 4 * g + q) * LD + col0 + 4 * p;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a0));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a1));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-__device__ __forceinline__ uint32_t cvt_pk(float lo, float hi) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){lo, hi}, bf16x2));
-}
-__device__ __forceinline__ bf16x8 pack_pi(const f32x4& a, const f32x4& b) {
-  const u32x4 u = {cvt_pk(a[0], a[1]), cvt_pk(a[2], a[3]), cvt_pk(b[0], b[1]), cvt_pk(b[2], b[3])};
-  return __builtin_bit_cast(bf16x8, u);
-}
-__device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
-// keep-bit b of a mask word as an all-ones / all-zeros 32-bit mask
-__device__ __forceinline__ float keep_bit(float v, uint32_t w, int b) {
-  return __int_as_float(__float_as_int(v) & __builtin_amdgcn_sbfe(w, b, 1));
-}
-__device__ __forceinline__ float quad_max(float v) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-  r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
 
 // 8 columns ks*32 + 8g .. of one row of a head, zeros where the row is out of range or the columns are
 // the padding of the reduction dimension (never a global read past the head's HD columns)

@@ -304,18 +304,15 @@ class BlockFn(torch.autograd.Function):
         qkv = torch.empty(M, 3 * D, dtype=c, device=dev)
         linear_bias(h1, qkvw, qkvb, qkv)
         flash = use_flash(N, D // H)
-        if flash and D // H != 64:
-            # head_dim 80 / 128: the bf16 kernels of csrc/attention_hd.hip (also under fp8_attn: there is no
-            # fp8 kernel at these widths); the keep-mask planes do not depend on head_dim
+        if flash:
             o = torch.empty(M, D, dtype=c, device=dev)
             lse = torch.empty(B, H, N, dtype=F32, device=dev)
             pm = premask[1] if premask is not None else None
-            P, Pd = None, ops.attn_fwd_hd(qkv, o, lse, B, N, H, D // H, scale, p_attn, seeds[0], mask=pm)
-        elif flash:
-            o = torch.empty(M, D, dtype=c, device=dev)
-            lse = torch.empty(B, H, N, dtype=F32, device=dev)
-            pm = premask[1] if premask is not None else None
-            if RT.attn_fp8:
+            if D // H != 64:
+                # head_dim 80 / 128: the bf16 kernels of csrc/attention_hd.hip (also under fp8_attn: there is no
+                # fp8 kernel at these widths); the keep-mask planes do not depend on head_dim
+                amask = ops.attn_fwd_hd(qkv, o, lse, B, N, H, D // H, scale, p_attn, seeds[0], mask=pm)
+            elif RT.attn_fp8:
                 # qkv is rounded in place to the fp8 grid: the saved tensor (and so the bf16 backward)
                 # sees exactly what the fp8 forward multiplied
                 ws = ops.attn_fp8_workspace(B, N, H, dev)
@@ -439,17 +436,16 @@ class BlockFn(torch.autograd.Function):
         do = torch.empty(M, D, dtype=c, device=dev)
         linear_dx_w(dprep, projw, do)
         del dprep
-        if flash and D // H != 64:
-            dqkv = torch.empty(M, 3 * D, dtype=c, device=dev)
-            dvec = torch.empty(B, H, N, dtype=F32, device=dev)
-            ops.attn_bwd_hd(qkv, o, do, lse, dvec, dqkv, B, N, H, D // H, scale, p_attn, seeds[0], mask=Pd,
-                            dbias=grad_buf(qkvb) if RT.attn_bias_grad else None)
-        elif flash:
+        if flash:
             dqkv = torch.empty(M, 3 * D, dtype=c, device=dev)
             dvec = torch.empty(B, H, N, dtype=F32, device=dev)
             # the qkv bias gradient comes out of the attention backward's epilogues (column partials of dqkv)
-            ops.attn_bwd(qkv, o, do, lse, dvec, dqkv, B, N, H, scale, p_attn, seeds[0], mask=Pd,
-                         dbias=grad_buf(qkvb) if RT.attn_bias_grad else None)
+            dbias = grad_buf(qkvb) if RT.attn_bias_grad else None
+            if D // H != 64:
+                ops.attn_bwd_hd(qkv, o, do, lse, dvec, dqkv, B, N, H, D // H, scale, p_attn, seeds[0], mask=Pd,
+                                dbias=dbias)
+            else:
+                ops.attn_bwd(qkv, o, do, lse, dvec, dqkv, B, N, H, scale, p_attn, seeds[0], mask=Pd, dbias=dbias)
         else:
             dqkv = as_dtype(_attn_mat_bwd(qkv, P, Pd, do, B, N, H, scale, p_attn, seeds[0]), c)
         del do
