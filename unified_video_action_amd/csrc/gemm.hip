@@ -15,7 +15,7 @@
 //    ds_read_b64_tr_b16 (hardware transpose) so no operand is ever transposed in HBM.
 //  * gemm_generic    -- fp32 FMA on the VALU, any shape / dtype; the fp32 parity
 //    path and the tiny-K/N projections (K = 2, 4, 10 ...).
-#include "common.h"
+#include "gemm_ring.h"
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -668,14 +668,12 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_bf16(const bf16* __restrict_
 // MFMA bf16 kernel v2: LDS-DMA staging (global_load_lds, 16 B/lane, no register pass)
 //   K-major image [128 rows][64 k]  (128-B rows), 16-B chunk c of row r stored at c ^ (r & 7)
 //   M-major image [64 k][128 rows]  (256-B rows), 16-B chunk c of row k stored at c ^ s(k),
-//       s(k) = ((k & 3) << 1) | (((k >> 3) & 1) << 3)  -> the ds_read_b64_tr_b16 fragment
+//       s(k) = ring_kswz<256>(k) (gemm_ring.h)  -> the ds_read_b64_tr_b16 fragment
 //       reads of one 32-lane half hit 16 distinct chunks (conflict-free), no padding.
 // Both images are lane-linear per 1-KiB wave instruction, so the swizzle moves to the
 // per-lane SOURCE address (cdna_hip_programming.md rule 21).  OOB lanes read a zero page.
 // =====================================================================================
 __device__ __attribute__((aligned(16))) bf16 g_uva_zero_page[64];
-
-__device__ __forceinline__ int mswz(int k) { return ((k & 3) << 1) | (((k >> 3) & 1) << 3); }
 
 template <int T>
 __device__ __forceinline__ bf16x8 frag_load_v2(const bf16* lds, int row0, int ks) {
@@ -689,8 +687,8 @@ __device__ __forceinline__ bf16x8 frag_load_v2(const bf16* lds, int row0, int ks
     const int k = ks * 32 + g * 8 + q;
     const int col = row0 + 4 * p;  // element column, 4 elements (8 B) inside one 16-B chunk
     const int c = col >> 3, w = col & 7;
-    const bf16* a0 = lds + k * 128 + ((c ^ mswz(k)) << 3) + w;
-    const bf16* a1 = lds + (k + 4) * 128 + ((c ^ mswz(k + 4)) << 3) + w;
+    const bf16* a0 = lds + k * 128 + ((c ^ ring_kswz<256>(k)) << 3) + w;
+    const bf16* a1 = lds + (k + 4) * 128 + ((c ^ ring_kswz<256>(k + 4)) << 3) + w;
     s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a0));
     s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a1));
     s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -717,7 +715,7 @@ __device__ __forceinline__ const bf16* dma_addr(const bf16* __restrict__ P, long
     return (gr < nrows && k < K) ? P + (long long)gr * ld + k : g_uva_zero_page;
   } else if (T == 1) {
     const int kr = e >> 7, cl = (e & 127) >> 3;
-    const int m = (cl ^ mswz(kr)) << 3;
+    const int m = (cl ^ ring_kswz<256>(kr)) << 3;
     const int gk = k0 + kr, gr = row0 + m;
     return (gr < nrows && gk < K) ? P + (long long)gk * ld + gr : g_uva_zero_page;
   } else {
@@ -1428,13 +1426,8 @@ __global__ __launch_bounds__(512, 1) void gemm_8ph(const bf16* __restrict__ A, c
   }
 }
 
-// UVA_GEMM_PERSIST: the default of the run-time switch uva_gemm_set_persist (0: gemm_8ph only, measured
-// faster; 1: gemm_8pp where eligible); diagnostic bits 2 (one tile per workgroup) and 4 (next tile's DMA
-// after the epilogue)
-#ifndef UVA_GEMM_PERSIST
-#define UVA_GEMM_PERSIST 0
-#endif
-static int g_gemm_persist = UVA_GEMM_PERSIST & 1;
+// the run-time switch uva_gemm_set_persist (0: gemm_8ph only, measured faster; 1: gemm_8pp where eligible)
+static int g_gemm_persist = 0;
 extern "C" int uva_gemm_set_persist(int on) {
   const int prev = g_gemm_persist;
   if (on >= 0) g_gemm_persist = on ? 1 : 0;
@@ -1562,8 +1555,7 @@ __global__ __launch_bounds__(512, 1) void gemm_8pp(const bf16* __restrict__ A, c
   for (;;) {
     if (!first) {
       // K-tile 0 of this tile was issued before the previous tile's E epilogue stores
-      if constexpr ((UVA_GEMM_PERSIST & 4) != 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W0) : "memory");
-      else if (has_aux) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WEA) : "memory");
+      if (has_aux) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WEA) : "memory");
       else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WE) : "memory");
     }
     first = false;
@@ -1675,7 +1667,7 @@ __global__ __launch_bounds__(512, 1) void gemm_8pp(const bf16* __restrict__ A, c
       tile_of(pid, m0, n0);
       offsets(m0, n0);
     }
-    if constexpr (!(UVA_GEMM_PERSIST & 4)) stage01();
+    stage01();
     asm volatile("" ::: "memory");
     // ---- register epilogue (no LDS): 8 consecutive columns per lane per fragment pair
     EpiRow none;
@@ -1697,24 +1689,9 @@ __global__ __launch_bounds__(512, 1) void gemm_8pp(const bf16* __restrict__ A, c
         epi_apply_row8<TC>(C, (long long)row * ldc + col, ep, bv[p], none, row, col, 0, M, N, v, o);
       }
     }
-    if constexpr ((UVA_GEMM_PERSIST & 4) != 0) {  // diagnostic: next tile's DMA after the epilogue
-      asm volatile("" ::: "memory");
-      stage01();
-    }
     if (!more) break;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the restaged DMAs land before the LDS is released
-}
-
-// number of compute units of the current device (persistent grids)
-static int device_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
 }
 
 template <typename TC>
@@ -1916,8 +1893,7 @@ static int launch_8ph(int ta, int tb, const void* A, const void* B, void* C, int
                        ep.gate == nullptr && ep.beta == 0.f && ep.res_grad == 0 && ldc % 8 == 0 &&
                        (((uintptr_t)C | (uintptr_t)ep.aux | (uintptr_t)ep.bias) % 16) == 0;
   if (persist) {
-    // (UVA_GEMM_PERSIST & 2: diagnostic, one tile per workgroup)
-    const unsigned g = (UVA_GEMM_PERSIST & 2) ? (unsigned)nblk : (unsigned)std::min<long long>(nblk, (long long)device_cus());
+    const unsigned g = (unsigned)std::min<long long>(nblk, (long long)ring_cus());
 #define G8P(a, b, BNV)                                                                                        do {                                                                                                          static bool attr = false;                                                                                   const int lb = Gemm8Cfg<BNV>::LDS_BYTES;                                                                    if (!attr) {                                                                                                  (void)hipFuncSetAttribute((const void*)gemm_8pp<a, b, BNV, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, lb);       attr = true;                                                                                              }                                                                                                           gemm_8pp<a, b, BNV, TC><<<dim3(g), 512, lb, s>>>((const bf16*)A, (const bf16*)B, (TC*)C, M, N, K, lda, ldb, ldc, ep);   } while (0)
 #define G8PC(a, b) do { if (bn == 384) G8P(a, b, 384); else G8P(a, b, 256); } while (0)
     if (ta == 0 && tb == 0) G8PC(0, 0);
@@ -1950,19 +1926,6 @@ static int launch_8ph(int ta, int tb, const void* A, const void* B, void* C, int
   }
   return 1;
 }
-
-extern "C" int uva_gemm4_try(int out_dtype, const void* A, const void* B, void* C, int M, int N, int K,
-                             long long lda, long long ldb, long long ldc, const float* bias, float alpha,
-                             hipStream_t s);
-extern "C" int uva_gemm8w_try(int out_dtype, const void* A, const void* B, void* C, int M, int N, int K,
-                              long long lda, long long ldb, long long ldc, const float* bias, float alpha,
-                              hipStream_t s);
-extern "C" int uva_gemm8w_tt_try(const void* A, const void* B, float* C, int M, int N, int K, long long lda,
-                                 long long ldb, long long ldc, float alpha, float beta, float* ws, long long ws_floats,
-                                 int* reduce, hipStream_t s);
-extern "C" int uva_gemm4_tt_try(const void* A, const void* B, float* C, int M, int N, int K, long long lda,
-                                long long ldb, long long ldc, float alpha, float beta, float* ws, long long ws_floats,
-                                int* reduce, hipStream_t s);
 
 template <typename TC>
 static int launch_mfma(int ta, int tb, const void* A, const void* B, void* C, int M, int N, int K, long long lda,

@@ -27,9 +27,8 @@
 // Tails: rows / columns past M / N read zeros through the buffer descriptors' range check and are
 // masked at the store.  The hipBLASLt kernels this replaces use the same 4-wave / 256-thread /
 // AGPR-accumulator geometry (profiles/r04/ab_gemm_persist.txt).
-#include "common.h"
+#include "gemm_ring.h"
 
-#include <algorithm>
 #include <type_traits>
 
 // diagnostic builds only (tools/build_variant.py gemm4.hip -DUVA_G4_DIAG=n; results are WRONG): bit 1 no
@@ -46,39 +45,10 @@
 #ifndef UVA_G4_SPREAD
 #define UVA_G4_SPREAD 48
 #endif
-#ifndef UVA_G4_ROT
-#define UVA_G4_ROT 0
-#endif
-#ifndef UVA_G4_TBLK
-#define UVA_G4_TBLK 0
-#endif
 
-
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-namespace {
-
-template <int FM_, int FN_>
-struct G4Cfg {
-  static constexpr int FM = FM_, FN = FN_;
-  static constexpr int BM = 32 * FM, BN = 32 * FN;               // block tile
-  static constexpr int GA = BM / 32, GB = BN / 32, G = GA + GB;  // DMA instructions per thread per K-tile
-  static constexpr int A_BYTES = BM * 128, REGION = (BM + BN) * 128, RING = 2 * REGION;
-};
-
-// 16-B chunk swizzle of a k-major image row [64 k][W] (T = 1 operands), chosen so that the 8 rows
-// {8g + q} a 32-lane group of ds_read_b64_tr_b16 touches (32 B each) fall on 8 distinct 32-B bank
-// slots: 512-B rows (W = 256) all start on one bank -> XOR by 8 distinct even chunk offsets; 384-B rows
-// (W = 192) alternate between two bank halves -> 4 offsets within 128 B suffice (and keep the XOR
-// inside each 8-chunk group of the 24-chunk row)
-template <int W>
-__device__ __forceinline__ int g4_kswz(int k) {
-  static_assert(W == 256 || W == 192, "row width");
-  if constexpr (W == 256) return ((k & 3) << 1) | (((k >> 3) & 1) << 3);
-  else return (((k >> 1) & 1) << 1) | (((k >> 3) & 1) << 2);
-}
-
-}  // namespace
+// 4 waves as 2 (M) x 2 (N), 16 FM x 16 FN per wave: a 32 FM x 32 FN block tile on the shared ring
+template <int FM, int FN>
+using G4Cfg = RingCfg<32 * FM, 32 * FN, 4>;
 
 // TA / TB: 0 = K-contiguous operand (A [M][K], B [N][K]); 1 = M- / N-contiguous (A [K][M], B [K][N]: the
 // dW products, mar_con_unified.py Block backward).  SPLIT: work items are (tile, K-slice) pairs writing
@@ -117,14 +87,10 @@ __global__ __launch_bounds__(256, 1) void gemm_4w(const bf16* __restrict__ A, co
 
   // item pid -> (tile: GROUP-8 raster, K-slice); slices are the slow index (concurrent items share one
   // K range, so neighbouring tiles share operand rows in L2)
-  constexpr int GROUP = 8;
   auto item_of = [&](int pid, int& m0, int& n0, int& kb, int& nkt, int& t) __attribute__((always_inline)) {
     const int sl = pid / ntiles;
     t = pid - sl * ntiles;
-    const int group = t / (GROUP * tn), first_m = group * GROUP;
-    const int gsz = min(tm - first_m, GROUP);
-    m0 = (first_m + (t % (GROUP * tn)) % gsz) * G::BM;
-    n0 = ((t % (GROUP * tn)) / gsz) * G::BN;
+    ring_tile<G::BM, G::BN>(t, tm, tn, m0, n0);
     kb = sl * kps;
     nkt = (min(K, kb + kps) - kb) / 64;
   };
@@ -133,48 +99,19 @@ __global__ __launch_bounds__(256, 1) void gemm_4w(const bf16* __restrict__ A, co
       (void*)A, 0, (int)(unsigned)min(2ull * (unsigned long long)(TA ? K : M) * (unsigned)lda, 0xffffffffull), 0x00020000);
   const auto rsB = __builtin_amdgcn_make_buffer_rsrc(
       (void*)B, 0, (int)(unsigned)min(2ull * (unsigned long long)(TB ? K : N) * (unsigned)ldb, 0xffffffffull), 0x00020000);
-  // per-lane source offsets of the DMA target item.  T = 0: instruction i of wave w covers image rows
-  // 8 (w G + i) .. +7 of 128 B; lane l: row (l >> 3), LDS chunk (l & 7) <- global chunk (l & 7) ^ (row & 7).
-  // T = 1: the k-major image [64][W] taken 1 KB per instruction in byte order; lane l of instruction j:
-  // byte j KB + 16 l -> (k, chunk), global chunk = chunk ^ kswz(k).  The K-tile step is the soffset
-  // (128 B for T = 0, 64 rows of ld for T = 1).
-  auto lane_src = [&](auto TC_, auto WC, int i, int gi, int ld) __attribute__((always_inline)) -> unsigned {
-    constexpr int T = decltype(TC_)::value, W = decltype(WC)::value;
-    if constexpr (T == 0) {
-      const int row = 8 * (w * gi + i) + (lane >> 3);
-      return (unsigned)row * (unsigned)ld * 2u + (unsigned)(((lane & 7) ^ (row & 7)) * 16);
-    } else {
-#if UVA_G4_TBLK
-      // blocked image [W / 64][64 k][64 cols]: instruction j = 8 k-rows x 128 B of one 64-col block
-      const int j = w * gi + i, k = 8 * (j & 7) + (lane >> 3);
-      return (unsigned)k * (unsigned)ld * 2u + (unsigned)((j >> 3) * 128 + (((lane & 7) ^ g4_kswz<192>(k)) * 16));
-#else
-      const int b = (w * gi + i) * 1024 + lane * 16;
-      const int k = b / (W * 2), c = (b % (W * 2)) >> 4;
-      return (unsigned)k * (unsigned)ld * 2u + (unsigned)((c ^ g4_kswz<W>(k)) * 16);
-#endif
-    }
-  };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using WAc = std::integral_constant<int, G::BM>;
-  using WBc = std::integral_constant<int, G::BN>;
+  // per-lane source offsets of the DMA target item: instruction i of wave w is piece w G + i of its image
+  // (gemm_ring.h); the K-tile step is the soffset (128 B for T = 0, 64 rows of ld for T = 1)
   unsigned offA[G::GA], offB[G::GB];
-  int rot_o = 0, nkt_o = 0;  // the offsets' item: K-tile rotation, K-tile count
   auto dma_offsets = [&](int pid) __attribute__((always_inline)) {
     int m0, n0, kb, nkt, t;
     item_of(pid, m0, n0, kb, nkt, t);
-    nkt_o = nkt;
-    rot_o = UVA_G4_ROT ? ((t % (UVA_G4_ROT > 0 ? UVA_G4_ROT : 1)) * 2) % nkt : 0;
-    // the item's origin (uniform): T = 0 rows m0, column kb; T = 1 row kb, column m0
-    const unsigned a0 = (unsigned)__builtin_amdgcn_readfirstlane(TA ? (kb * lda + m0) * 2 : (m0 * lda + kb) * 2);
-    const unsigned b0 = (unsigned)__builtin_amdgcn_readfirstlane(TB ? (kb * ldb + n0) * 2 : (n0 * ldb + kb) * 2);
+    const unsigned a0 = ring_origin<TA>(m0, kb, lda), b0 = ring_origin<TB>(n0, kb, ldb);
 #pragma unroll
     for (int i = 0; i < G::GA; ++i)
-      offA[i] = a0 + (TA ? lane_src(I1{}, WAc{}, i, G::GA, lda) : lane_src(I0{}, WAc{}, i, G::GA, lda));
+      offA[i] = a0 + (TA ? ring_src_k<G::BM>(lane, w * G::GA + i, lda) : ring_src(lane, w * G::GA + i, lda));
 #pragma unroll
     for (int i = 0; i < G::GB; ++i)
-      offB[i] = b0 + (TB ? lane_src(I1{}, WBc{}, i, G::GB, ldb) : lane_src(I0{}, WBc{}, i, G::GB, ldb));
+      offB[i] = b0 + (TB ? ring_src_k<G::BN>(lane, w * G::GB + i, ldb) : ring_src(lane, w * G::GB + i, ldb));
   };
 #if UVA_G4_DIAG & 32
   // timing only: every K-tile re-reads the item's first K-tile (operands resident in L2)
@@ -184,51 +121,24 @@ __global__ __launch_bounds__(256, 1) void gemm_4w(const bf16* __restrict__ A, co
 #endif
   // DMA instruction i (A first) of K-tile kt of the offsets' item into region r
   auto dma_one = [&](int r, int i, int kt) __attribute__((always_inline)) {
-    if (i < G::GA)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rsA, (__attribute__((address_space(3))) void*)(smem + r * G::REGION + (w * G::GA + i) * 1024), 16,
-          (int)offA[i < G::GA ? i : 0], __builtin_amdgcn_readfirstlane(kt * stepA), 0, 0);
-    else
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rsB, (__attribute__((address_space(3))) void*)(smem + r * G::REGION + G::A_BYTES + (w * G::GB + i - G::GA) * 1024),
-          16, (int)offB[i < G::GA ? 0 : i - G::GA], __builtin_amdgcn_readfirstlane(kt * stepB), 0, 0);
+    ring_dma<G>(smem, w, r, i, rsA, rsB, offA, offB, kt, stepA, stepB);
   };
   dma_offsets(slot);
-  auto kphys = [&](int kt) __attribute__((always_inline)) {
-    const int k = kt + rot_o;
-    return k >= nkt_o ? k - nkt_o : k;
-  };
 
-  // fragment reads of 16 rows (m or n) x 32 k, half h of a K-tile.  T = 0: row (lane & 15), 16-B chunk
-  // h*4 + (lane >> 4) of a 128-B row (XOR row & 7).  T = 1: two ds_read_b64_tr_b16 of the k-major image
-  // (rows k and k + 4 of the lane's quad, 4 columns each), the hardware transpose gathering the lane's
-  // 8 consecutive k (as gemm_8ph's frag8)
+  // fragment reads of 16 rows (m or n) x 32 k, half h of a K-tile (gemm_ring.h): T = 0 one ds_read_b128
+  // of 16 image rows at the lane's offset, T = 1 the k-major image's transposing read
   const int lrow = lane & 15;
-  const int lofs0 = lrow * 128 + ((((lane >> 4)) ^ (lrow & 7)) << 4);
-  const int lofs1 = lrow * 128 + (((4 + (lane >> 4)) ^ (lrow & 7)) << 4);
+  const int lofs0 = ring_lofs<0>(lane, lrow), lofs1 = ring_lofs<1>(lane, lrow);
   const int a0o = wr * (FM * 16), b0o = wc * (FN * 16);  // first row (T = 0) / column (T = 1) of the wave
   auto frag = [&](auto TC_, auto WC, int base, int r0, int h) __attribute__((always_inline)) -> bf16x8 {
     constexpr int T = decltype(TC_)::value, W = decltype(WC)::value;
-    if constexpr (T == 0) {
-      return *(const bf16x8*)(smem + base + r0 * 128 + (h ? lofs1 : lofs0));
-    } else {
-      const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-      const int k = h * 32 + g * 8 + q;
-      const int col = r0 + 4 * p;
-      const int c = col >> 3, o = (col & 7) * 2;
-#if UVA_G4_TBLK
-      const char* a0 = smem + base + (c >> 3) * 8192 + k * 128 + (((c & 7) ^ g4_kswz<192>(k)) << 4) + o;
-      const char* a1 = smem + base + (c >> 3) * 8192 + (k + 4) * 128 + (((c & 7) ^ g4_kswz<192>(k + 4)) << 4) + o;
-#else
-      const char* a0 = smem + base + k * W * 2 + ((c ^ g4_kswz<W>(k)) << 4) + o;
-      const char* a1 = smem + base + (k + 4) * W * 2 + ((c ^ g4_kswz<W>(k + 4)) << 4) + o;
-#endif
-      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a0));
-      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a1));
-      const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      return __builtin_bit_cast(bf16x8, v);
-    }
+    if constexpr (T == 0) return *(const bf16x8*)(smem + base + r0 * 128 + (h ? lofs1 : lofs0));
+    else return ring_frag_k<W>(smem + base, lane, r0, h);
   };
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  using WAc = std::integral_constant<int, G::BM>;
+  using WBc = std::integral_constant<int, G::BN>;
   auto fragA = [&](int r, int f, int h) __attribute__((always_inline)) {
     return TA ? frag(I1{}, WAc{}, r * G::REGION, a0o + f * 16, h) : frag(I0{}, WAc{}, r * G::REGION, a0o + f * 16, h);
   };
@@ -242,9 +152,9 @@ __global__ __launch_bounds__(256, 1) void gemm_4w(const bf16* __restrict__ A, co
 
   // prologue: K-tiles 0 and 1 into regions 0 and 1, wait for region 0, read substep 0's fragments
 #pragma unroll
-  for (int i = 0; i < G::G; ++i) dma_one(0, i, kphys(0));
+  for (int i = 0; i < G::G; ++i) dma_one(0, i, 0);
 #pragma unroll
-  for (int i = 0; i < G::G; ++i) dma_one(1, i, kphys(1));
+  for (int i = 0; i < G::G; ++i) dma_one(1, i, 1);
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::G) : "memory");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
@@ -378,11 +288,10 @@ __global__ __launch_bounds__(256, 1) void gemm_4w(const bf16* __restrict__ A, co
   using ZF = std::integral_constant<bool, false>;
   // two K-tiles (regions 0, 1); their odd substeps refill with K-tiles kt0 and kt0 + 1 of the offsets' item
   auto group = [&](auto ZC, bool post, int kt0) __attribute__((always_inline)) {
-    const int ka = UVA_G4_ROT ? kphys(kt0) : kt0, kb = UVA_G4_ROT ? kphys(kt0 + 1) : kt0 + 1;
-    substep(U0{}, ZC, false, ka);
-    substep(U1{}, ZF{}, post, ka);
-    substep(U2{}, ZF{}, false, kb);
-    substep(U3{}, ZF{}, false, kb);
+    substep(U0{}, ZC, false, kt0);
+    substep(U1{}, ZF{}, post, kt0);
+    substep(U2{}, ZF{}, false, kt0 + 1);
+    substep(U3{}, ZF{}, false, kt0 + 1);
   };
 
   for (int ii = 0; ii < my_items; ++ii) {
@@ -413,51 +322,28 @@ __global__ __launch_bounds__(256, 1) void gemm_4w(const bf16* __restrict__ A, co
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int g4_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 // -1 = automatic; otherwise the configuration index (1: 256 x 192)
 static int g_gemm4_force = -1;
 static int g_gemm4_on = 1;
 
 struct G4Choice {
-  int cfg;  // 0: 256x256 NS4, 1: 256x192 NS4 ; -1 none
+  int cfg;  // 1: 256 x 192 (0 was 256 x 256: not built) ; -1 none
   int grid;
 };
 
 static G4Choice g4_plan(int M, int N, int K) {
   G4Choice c{-1, 0};
-  const int cus = g4_cus();
+  const int cus = ring_cus();
   if (K % 128 != 0 || K < 256 || M < 256 || N < 128) return c;
   // 256 x 256 (FN = 8: 256 accumulator AGPRs) is not built: with every AGPR holding an accumulator
   // hipcc shuffles accumulators through VGPRs inside the K loop (644 v_accvgpr_read / 480 _write per
   // tile body vs 192 / 0 for FN = 6); 256 x 192 tiles also divide the Block's N = 768 / 2304 / 3072
-  // into whole rounds of 256 CUs at M = 32768
-  const int BNs[2] = {256, 192};
-  double best = -1.0;
-  for (int i = 1; i < 2; ++i) {
-    if (g_gemm4_force >= 0 && g_gemm4_force != i) continue;
-    const int bn = BNs[i];
-    if ((long long)((N + bn - 1) / bn) * bn * 4 + (i == 0 ? 131072 : 114688) > 163840) continue;  // bias in LDS
-    const long long tiles = (long long)((M + 255) / 256) * ((N + bn - 1) / bn);
-    const long long rounds = (tiles + cus - 1) / cus;
-    const double occ = (double)tiles / (double)(rounds * cus);
-    const double useful = (double)M * N / ((double)tiles * 256 * bn);
-    // per-CU efficiency of the 256 x 192 tile relative to 256 x 256 (fewer MFMAs per staged byte)
-    const double eff = occ * useful * (bn == 192 ? 0.97 : 1.0);
-    if (eff > best + 1e-9) {
-      best = eff;
-      c.cfg = i;
-      c.grid = (int)(tiles < cus ? tiles : cus);
-    }
-  }
+  // into whole rounds of 256 CUs at M = 32768.  So 256 x 192 (index 1) is the one configuration
+  if (g_gemm4_force >= 0 && g_gemm4_force != 1) return c;
+  if ((long long)((N + 191) / 192) * 192 * 4 + G4Cfg<8, 6>::RING > 163840) return c;  // bias in LDS
+  const long long tiles = (long long)((M + 255) / 256) * ((N + 191) / 192);
+  c.cfg = 1;
+  c.grid = (int)(tiles < cus ? tiles : cus);
   return c;
 }
 
@@ -505,65 +391,27 @@ extern "C" int uva_gemm4_try(int out_dtype, const void* A, const void* B, void* 
   return r ? -r : 1;
 }
 
-// dW products (A [K][M], B [K][N], both M- / N-contiguous; K = tokens): split-K plan -- enough (tile,
-// K-slice) items for one round of the chip, slices of whole 128-deep pairs, >= 4 K-tiles each
-struct G4Split {
-  int splits, kps, grid;
-};
-static G4Split g4_plan_tt(int M, int N, int K, long long ws_floats, bool need_ws) {
-  G4Split p{0, 0, 0};
-  if (K % 128 != 0 || K < 256 || M < 256 || N < 192) return p;
-  const int cus = g4_cus();
-  const long long tiles = (long long)((M + 255) / 256) * ((N + 191) / 192);
-  // measured against gemm_8ph (tools/gemm4_bench.py dw): ahead on 768 x 768 (12 tiles, 20 slices:
-  // 62 vs 68 us at 32768 tokens), level on 2304 x 768, 20-25 % behind on 3072 x 768 / 768 x 3072 (the
-  // k-major loads' latency: a 4-wave CU cannot keep enough of them in flight) -- few-tile products only
-  if (tiles > 16) return p;
-  int splits = (int)std::max<long long>(1, (cus + tiles / 2) / tiles);
-  if (splits > K / 256) splits = K / 256;
-  while (splits > 1 && (long long)splits * M * N > ws_floats) --splits;
-  if (splits == 1 && need_ws && (long long)M * N > ws_floats) return p;
-  int kps = K;
-  for (; splits > 1; --splits) {
-    kps = ((K + splits - 1) / splits + 127) / 128 * 128;
-    const int sp = (K + kps - 1) / kps;
-    if (K - (sp - 1) * kps >= 256) {
-      splits = sp;
-      break;
-    }
-  }
-  if (splits <= 1) {
-    splits = 1;
-    kps = K;
-  }
-  p.splits = splits;
-  p.kps = kps;
-  p.grid = (int)std::min<long long>(tiles * splits, cus);
-  return p;
+// dW products: the shared split-K plan (gemm_ring.h), few-tile products only.  Measured against gemm_8ph
+// (tools/gemm4_bench.py dw): ahead on 768 x 768 (12 tiles, 20 slices: 62 vs 68 us at 32768 tokens), level on
+// 2304 x 768, 20-25 % behind on 3072 x 768 / 768 x 3072 (the k-major loads' latency: a 4-wave CU cannot keep
+// enough of them in flight)
+static RingSplit g4_plan_tt(int M, int N, int K, long long ws_floats, bool need_ws) {
+  return ring_plan_tt(M, N, K, ws_floats, need_ws, 16);
 }
 
-// 1 = launched: *reduce = 0 -> C holds alpha * A^T B; *reduce = s > 0 -> ws holds s fp32 partial slabs of
-// M x N (ld N), the caller reduces them into C (alpha, beta).  0 = not eligible, < 0 = -hipError
+// the dW products (return values: gemm_ring.h)
 extern "C" int uva_gemm4_tt_try(const void* A, const void* B, float* C, int M, int N, int K, long long lda,
                                 long long ldb, long long ldc, float alpha, float beta, float* ws, long long ws_floats,
                                 int* reduce, hipStream_t s) {
   *reduce = 0;
   if (!g_gemm4_on) return 0;
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  if (lda % 8 || ldb % 8 || ldc % 8 || M % 8 || N % 8 || lda < M || ldb < N) return 0;
-  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)ws) % 16) return 0;
-  if (2.0 * (double)K * (double)lda >= 2147483648.0 || 2.0 * (double)K * (double)ldb >= 2147483648.0) return 0;
-  const G4Split p = g4_plan_tt(M, N, K, ws ? ws_floats : 0, beta != 0.f);
-  if (p.splits == 0) return 0;
-  // the C (or slab workspace) byte range must fit the store descriptor (see uva_gemm4_try)
-  if (p.splits == 1 && beta == 0.f ? (double)M * (double)ldc * 4.0 > (double)0x7fff0000
-                                   : (double)p.splits * (double)M * (double)N * 4.0 > (double)0x7fff0000)
-    return 0;
+  const RingSplit p = g4_plan_tt(M, N, K, ws ? ws_floats : 0, beta != 0.f);
+  const bool direct = p.splits == 1 && beta == 0.f;
+  if (!ring_tt_ok(A, B, C, ws, M, N, K, lda, ldb, ldc, p, direct)) return 0;
   int r;
-  if (p.splits == 1 && beta == 0.f) {
+  if (direct) {
     r = g4_launch<8, 6, 1, 1, float>(A, B, C, M, N, K, lda, ldb, ldc, nullptr, alpha, p.grid, 1, K, 0, s);
   } else {
-    if (!ws) return 0;
     r = g4_launch<8, 6, 1, 1, float>(A, B, ws, M, N, K, lda, ldb, N, nullptr, 1.f, p.grid, p.splits, p.kps,
                                      (long long)M * N, s);
     *reduce = p.splits;
@@ -586,6 +434,6 @@ extern "C" long long uva_gemm4_plan(int M, int N, int K) {
 }
 
 extern "C" long long uva_gemm4_plan_tt(int M, int N, int K, long long ws_floats) {
-  const G4Split p = g4_plan_tt(M, N, K, ws_floats, true);
+  const RingSplit p = g4_plan_tt(M, N, K, ws_floats, true);
   return p.splits == 0 ? -1 : (long long)p.splits | ((long long)p.grid << 8);
 }

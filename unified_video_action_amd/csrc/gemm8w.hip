@@ -21,44 +21,22 @@
 //          pre-activation (C2, bf16) -- bit-identical to dX GEMM -> act_bwd_bias -- and the column sums of C
 //          (fc1's bias gradient) as per-64-row partials, part[(m0 + 64 wr) / 64][n], reduced by
 //          colsum_final in a second launch (the same values summed in another order than act_bwd_bias).
-#include "common.h"
+#include "gemm_ring.h"
 
-#include <algorithm>
+#include <climits>
 #include <type_traits>
-
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 // diagnostics (tools/build_variant.py gemm8w.hip -DUVA_G8_DBG=n): 1 no EPI 3 column partials, 2 s_nop after each
 // EPI 3 store, 4 vmcnt(0) after a tile's epilogue
 #ifndef UVA_G8_DBG
 #define UVA_G8_DBG 0
 #endif
-// 1: EPI 3 row inputs (the saved pre-activation) loaded one fragment row ahead; 0: each segment loads its own just
-// before use.  (EPI 2's residual rows ahead measured no faster: fc2 157 vs 154 us, profiles/r06/g8w_prefetch.txt)
-#ifndef UVA_G8_PREFETCH
-#define UVA_G8_PREFETCH 1
-#endif
+
+// NW waves as NW / 2 (M) x 2 (N), 16 FM x 16 FN per wave, on the shared ring
+template <int FM, int FN, int NW>
+using G8Cfg = RingCfg<16 * FM * (NW / 2), 32 * FN, NW>;
 
 namespace {
-
-template <int FM_, int FN_, int NW_>
-struct G8Cfg {
-  static constexpr int FM = FM_, FN = FN_, NW = NW_;
-  static constexpr int WM = NW / 2, WN = 2;                       // wave grid
-  static constexpr int BM = 16 * FM * WM, BN = 16 * FN * WN;      // block tile
-  static constexpr int GA = BM / (8 * NW), GB = BN / (8 * NW), G = GA + GB;  // DMA instructions per wave per K-tile
-  static constexpr int A_BYTES = BM * 128, REGION = (BM + BN) * 128, RING = 2 * REGION;
-  static_assert(GA * 8 * NW == BM && GB * 8 * NW == BN, "DMA split");
-};
-
-// 16-B chunk swizzle of a k-major image row [64 k][W] (TA / TB = 1 operands), as gemm4.hip's: the 8 rows a
-// 32-lane group of ds_read_b64_tr_b16 touches fall on distinct 32-B bank slots
-template <int W>
-__device__ __forceinline__ int g8_kswz(int k) {
-  static_assert(W == 256 || W == 192, "row width");
-  if constexpr (W == 256) return ((k & 3) << 1) | (((k >> 3) & 1) << 3);
-  else return (((k >> 1) & 1) << 1) | (((k >> 3) & 1) << 2);
-}
 
 __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
   typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
@@ -127,72 +105,50 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_8w(const bf16* __restric
     __syncthreads();
   }
 
-  constexpr int GROUP = 8;
   // item -> (tile: GROUP-8 raster, K-slice sl: the slow index, so concurrent items share one K range)
   auto item_of = [&](int pid, int& m0, int& n0) __attribute__((always_inline)) {
-    const int t = pid % ntiles;
-    const int group = t / (GROUP * tn), first_m = group * GROUP;
-    const int gsz = min(tm - first_m, GROUP);
-    m0 = (first_m + (t % (GROUP * tn)) % gsz) * G::BM;
-    n0 = ((t % (GROUP * tn)) / gsz) * G::BN;
+    ring_tile<G::BM, G::BN>(pid % ntiles, tm, tn, m0, n0);
   };
 
   const auto rsA = __builtin_amdgcn_make_buffer_rsrc(
       (void*)A, 0, (int)(unsigned)(2ull * (unsigned)(TA ? K : M) * (unsigned)lda), 0x00020000);
   const auto rsB = __builtin_amdgcn_make_buffer_rsrc(
       (void*)B, 0, (int)(unsigned)(2ull * (unsigned)(TB ? K : N) * (unsigned)ldb), 0x00020000);
-  // T = 1: the k-major image [64][W] taken 1 KB per DMA instruction in byte order; lane l of piece j: byte
-  // j KB + 16 l -> (k, chunk), global chunk = chunk ^ kswz(k)
-  auto lane_src_k = [&](auto WC, int piece, int ld) __attribute__((always_inline)) -> unsigned {
-    constexpr int W = decltype(WC)::value;
-    const int b = piece * 1024 + lane * 16;
-    const int k = b / (W * 2), c = (b % (W * 2)) >> 4;
-    return (unsigned)k * (unsigned)ld * 2u + (unsigned)((c ^ g8_kswz<W>(k)) * 16);
-  };
   using WAc = std::integral_constant<int, G::BM>;
   using WBc = std::integral_constant<int, G::BN>;
   constexpr int stepA = TA ? 0 : 128, stepB = TB ? 0 : 128;  // bytes per K-tile (T = 1: 64 rows of ld, runtime)
   const int stA = TA ? 64 * lda * 2 : stepA, stB = TB ? 64 * ldb * 2 : stepB;
-  // per-lane DMA sources: instruction i of wave w covers image rows 8 (w G + i) .. +7 of 128 B; lane l: row
-  // (l >> 3), LDS chunk (l & 7) <- global chunk (l & 7) ^ (row & 7); the K-tile step is the soffset
+  // per-lane DMA sources: instruction i of wave w is piece w G + i of its image (gemm_ring.h); the K-tile
+  // step is the soffset.  The T = 0 source is ring_src's value written out: called through the helper, every
+  // instantiation's prologue came out with its address arithmetic in another order
   unsigned offA[G::GA], offB[G::GB];
   auto dma_offsets = [&](int pid) __attribute__((always_inline)) {
     int m0, n0;
     item_of(pid, m0, n0);
     const int kb = (pid / ntiles) * kps;
-    const unsigned a0 = (unsigned)__builtin_amdgcn_readfirstlane(TA ? (kb * lda + m0) * 2 : (m0 * lda + kb) * 2);
-    const unsigned b0 = (unsigned)__builtin_amdgcn_readfirstlane(TB ? (kb * ldb + n0) * 2 : (n0 * ldb + kb) * 2);
+    const unsigned a0 = ring_origin<TA>(m0, kb, lda), b0 = ring_origin<TB>(n0, kb, ldb);
 #pragma unroll
     for (int i = 0; i < G::GA; ++i) {
       const int row = 8 * (w * G::GA + i) + (lane >> 3);
-      if constexpr (TA != 0) offA[i] = a0 + lane_src_k(WAc{}, w * G::GA + i, lda);
+      if constexpr (TA != 0) offA[i] = a0 + ring_src_k<G::BM>(lane, w * G::GA + i, lda);
       else offA[i] = a0 + (unsigned)row * (unsigned)lda * 2u + (unsigned)(((lane & 7) ^ (row & 7)) * 16);
     }
 #pragma unroll
     for (int i = 0; i < G::GB; ++i) {
       const int row = 8 * (w * G::GB + i) + (lane >> 3);
-      if constexpr (TB != 0) offB[i] = b0 + lane_src_k(WBc{}, w * G::GB + i, ldb);
+      if constexpr (TB != 0) offB[i] = b0 + ring_src_k<G::BN>(lane, w * G::GB + i, ldb);
       else offB[i] = b0 + (unsigned)row * (unsigned)ldb * 2u + (unsigned)(((lane & 7) ^ (row & 7)) * 16);
     }
   };
   auto dma_one = [&](int r, int i, int kt) __attribute__((always_inline)) {
-    if (i < G::GA)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rsA, (__attribute__((address_space(3))) void*)(smem + r * G::REGION + (w * G::GA + i) * 1024), 16,
-          (int)offA[i < G::GA ? i : 0], __builtin_amdgcn_readfirstlane(kt * stA), 0, 0);
-    else
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rsB, (__attribute__((address_space(3))) void*)(smem + r * G::REGION + G::A_BYTES + (w * G::GB + i - G::GA) * 1024),
-          16, (int)offB[i < G::GA ? 0 : i - G::GA], __builtin_amdgcn_readfirstlane(kt * stB), 0, 0);
+    ring_dma<G>(smem, w, r, i, rsA, rsB, offA, offB, kt, stA, stB);
   };
   dma_offsets(slot);
 
   const int lrow = lane & 15;
-  const int lofs0 = lrow * 128 + (((lane >> 4) ^ (lrow & 7)) << 4);
-  const int lofs1 = lrow * 128 + (((4 + (lane >> 4)) ^ (lrow & 7)) << 4);
+  const int lofs0 = ring_lofs<0>(lane, lrow), lofs1 = ring_lofs<1>(lane, lrow);
   const int a0o = wr * (FM * 16), b0o = wc * (FN * 16);
-  // T = 1: two ds_read_b64_tr_b16 of the k-major image (rows k and k + 4 of the lane's quad, 4 columns each),
-  // the hardware transpose gathering the lane's 8 consecutive k (the same k order as the T = 0 read).  The
+  // T = 1: the addresses of ring_frag_k (gemm_ring.h), formed another way to save registers.  The
   // swizzle of rows k, k + 4, k + 32, k + 36 is one lane constant sw (kswz reads bits 0-3 of k, q + 4 < 8) and
   // the fragment's 8-column chunk c0 / 8 is even and wave-uniform, so an address is lane constant + ((c0 / 8 ^
   // sw) << 4) + immediate: two VALU per fragment instead of a hoisted address register per (fragment, half)
@@ -200,14 +156,11 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_8w(const bf16* __restric
   const int kq = (lane >> 4) * 8 + ((lane >> 2) & 3);
   auto frag_k = [&](auto WC, int base, int c0, int h) __attribute__((always_inline)) -> bf16x8 {
     constexpr int W = decltype(WC)::value;
-    int sw = g8_kswz<W>(kq);
+    int sw = ring_kswz<W>(kq);
     asm volatile("" : "+v"(sw));
     const int lb = kq * W * 2 + ((lane >> 1) & 1) * 16 + (lane & 1) * 8;
     const char* a0 = smem + base + h * 32 * W * 2 + lb + (((c0 >> 3) ^ sw) << 4);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, a0 + 4 * W * 2));
-    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
+    return ring_read_tr(a0, a0 + 4 * W * 2);
   };
   auto fragA = [&](int r, int f, int h) __attribute__((always_inline)) {
     if constexpr (TA) return frag_k(WAc{}, r * G::REGION, a0o + f * 16, h);
@@ -402,7 +355,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_8w(const bf16* __restric
   auto seg_row = [&](int m0, int f) __attribute__((always_inline)) { return m0 + wr * (FM * 16) + f * 16 + lrow; };
   auto seg_col = [&](int n0, int p) __attribute__((always_inline)) { return n0 + wc * (FN * 16) + p * 32 + csub; };
   // immediate epilogue of one fragment row
-  constexpr bool PF = EPI == 3 && UVA_G8_PREFETCH;
+  constexpr bool PF = EPI == 3;
   auto epi_row = [&](int f, int m0, int n0, const RowIn (&in_row)[FN / 2]) __attribute__((always_inline)) {
 #pragma unroll
     for (int p = 0; p < FN / 2; ++p) {
@@ -414,8 +367,10 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_8w(const bf16* __restric
       finish(seg_row(m0, f), seg_col(n0, p), p, pk, v, in_row[p], PF);
     }
   };
-  // EPI 3 loads row f + 1's inputs before finishing row f (the wave otherwise sits in s_waitcnt for each
-  // segment's load: SQ_WAIT_ANY 0.47 of the kernel's cycles, profiles/r06/g8w_pmc.txt; 234 vs 255 us)
+  // EPI 3 loads row f + 1's inputs (the saved pre-activation) before finishing row f (the wave otherwise sits
+  // in s_waitcnt for each segment's load: SQ_WAIT_ANY 0.47 of the kernel's cycles, profiles/r06/g8w_pmc.txt;
+  // 234 vs 255 us).  EPI 2's residual rows ahead measured no faster: fc2 157 vs 154 us,
+  // profiles/r06/g8w_prefetch.txt
   RowIn in_buf[2][FN / 2];
   auto prefetch_in = [&](int f, int m0, int n0) __attribute__((always_inline)) {
     if constexpr (PF) {
@@ -562,9 +517,6 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_8w(const bf16* __restric
     }
     for (int it = it0; it < ngroups - 1; ++it) group(ZF{}, false, 2 * it + 2, -1, -1);
     dma_offsets(nxt);
-    // (UVA_G8_PREFETCH & 2: row 0's inputs issued before the tile's last K-group, ahead of its refill DMAs:
-    // older than every DMA the group's RAW waits count, so those waits only get stricter)
-    if constexpr ((UVA_G8_PREFETCH & 2) != 0) prefetch_in(0, m0, n0);
     group(ZF{}, false, 0, -1, -1);
     pack_def(n0);
     if constexpr (EPI == 3) {
@@ -573,7 +525,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_8w(const bf16* __restric
 #pragma unroll
         for (int e = 0; e < 8; ++e) cs[p][e] = 0.f;
     }
-    if constexpr ((UVA_G8_PREFETCH & 2) == 0) prefetch_in(0, m0, n0);
+    prefetch_in(0, m0, n0);
 #pragma unroll
     for (int f = 0; f < F0; ++f) {
       __builtin_amdgcn_sched_barrier(0);
@@ -626,16 +578,6 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_8w(const bf16* __restric
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int g8_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 static int g_gemm8w_on = 0;        // plain products (measurement switch; the fused forms are called directly)
 static int g_gemm8w_mode = 0;     // bit 1: 64 x 64 wave tiles; bits 2..4: deferred rows (64 x 64 only: 4);
                                   // bit 5 / 6: every product on two 4-wave workgroups per CU (NW = 4) / on
@@ -650,7 +592,7 @@ static int g8_launch1(const void* A, const void* B, void* C, int M, int N, int K
   using G = G8Cfg<4, FN, NW>;
   const int tn = (N + G::BN - 1) / G::BN;
   const long long tiles = (long long)((M + G::BM - 1) / G::BM) * tn;
-  const int grid = (int)std::min<long long>(tiles, (long long)g8_cus() * (8 / NW));
+  const int grid = (int)std::min<long long>(tiles, (long long)ring_cus() * (8 / NW));
   const int lds = G::RING + (NW == 8 && ep.bias ? tn * G::BN * 4 : 0);
   static bool attr = false;
   if (!attr) {
@@ -665,38 +607,6 @@ static int g8_launch1(const void* A, const void* B, void* C, int M, int N, int K
   return 0;
 }
 
-// dW products (A [K][M], B [K][N], K = tokens): split-K plan -- enough (tile, K-slice) items for one round of
-// the chip, slices of whole 128-deep pairs, >= 256 deep each
-struct G8Split {
-  int splits, kps, grid;
-};
-static G8Split g8_plan_tt(int M, int N, int K, long long ws_floats, bool need_ws) {
-  G8Split p{0, 0, 0};
-  if (K % 128 != 0 || K < 256 || M < 256 || N < 192) return p;
-  const int cus = g8_cus();
-  const long long tiles = (long long)((M + 255) / 256) * ((N + 191) / 192);
-  int splits = (int)std::max<long long>(1, (cus + tiles / 2) / tiles);
-  if (splits > K / 256) splits = K / 256;
-  while (splits > 1 && (long long)splits * M * N > ws_floats) --splits;
-  if (splits == 1 && need_ws && (long long)M * N > ws_floats) return p;
-  int kps = K;
-  for (; splits > 1; --splits) {
-    kps = ((K + splits - 1) / splits + 127) / 128 * 128;
-    const int sp = (K + kps - 1) / kps;
-    if (K - (sp - 1) * kps >= 256) {
-      splits = sp;
-      break;
-    }
-  }
-  if (splits <= 1) {
-    splits = 1;
-    kps = K;
-  }
-  p.splits = splits;
-  p.kps = kps;
-  p.grid = (int)std::min<long long>(tiles * splits, cus);
-  return p;
-}
 // rows of EPI 3 column-sum partials the launch writes (every wave of every row tile stores its 64 rows)
 static bool g8_nw4(int epi) { return (g_gemm8w_mode & 32) || (!(g_gemm8w_mode & 64) && epi == 3); }
 static int g8_part_rows(int M) { return g8_nw4(3) ? (M + 127) / 128 * 2 : (M + 255) / 256 * 4; }
@@ -749,24 +659,16 @@ static bool g8_ok(const void* A, const void* B, const void* C, int M, int N, int
 
 static uint32_t g8_key(unsigned long long seed) { return drop_key(seed); }
 
-// the dW products on gemm_8w (mode bit 7: 128): 1 = launched: *reduce = 0 -> C holds alpha * A^T B; *reduce = s > 0
-// -> ws holds s fp32 partial slabs of M x N (ld N) the caller reduces into C (alpha, beta).  0 = not eligible / off
+// the dW products on gemm_8w (mode bit 7: 128; return values: gemm_ring.h, 0 also when off)
 extern "C" int uva_gemm8w_tt_try(const void* A, const void* B, float* C, int M, int N, int K, long long lda,
                                  long long ldb, long long ldc, float alpha, float beta, float* ws, long long ws_floats,
                                  int* reduce, hipStream_t s) {
   *reduce = 0;
   if (!(g_gemm8w_mode & 128)) return 0;
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  if (lda % 8 || ldb % 8 || ldc % 8 || M % 8 || N % 8 || lda < M || ldb < N) return 0;
-  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)ws) % 16) return 0;
-  if (2.0 * (double)K * (double)lda >= 2147483648.0 || 2.0 * (double)K * (double)ldb >= 2147483648.0) return 0;
-  const G8Split p = g8_plan_tt(M, N, K, ws ? ws_floats : 0, beta != 0.f);
-  if (p.splits == 0) return 0;
+  // the shared split-K plan, any number of tiles
+  const RingSplit p = ring_plan_tt(M, N, K, ws ? ws_floats : 0, beta != 0.f, LLONG_MAX);
   const bool direct = p.splits == 1 && beta == 0.f;
-  if (direct ? (double)M * (double)ldc * 4.0 > (double)0x7fff0000
-             : (double)p.splits * (double)M * (double)N * 4.0 > (double)0x7fff0000)
-    return 0;
-  if (!direct && !ws) return 0;
+  if (!ring_tt_ok(A, B, C, ws, M, N, K, lda, ldb, ldc, p, direct)) return 0;
   using G = G8Cfg<4, 6, 8>;
   static bool attr = false;
   if (!attr) {
