@@ -67,6 +67,22 @@ int uva_gemm(int in_dtype, int out_dtype, int ta, int tb, const void* A, const v
  * 2 = MFMA LDS-DMA 128x128, 3 = MFMA 8-phase (256x256 or 128x384 tiles), splits = split-K slices. */
 long long uva_gemm_plan(int in_dtype, int ta, int tb, int M, int N, int K, int batch, int gn_prologue,
                         long long ws_floats);
+/* The route uva_gemm takes for exactly this argument set (uva_gemm's arguments without the stream: dtypes,
+ * pointers as they would be passed -- their alignment decides routes --, batch, every epilogue input, the
+ * workspace).  No device work and nothing is launched: uva_gemm's own dispatch and launchers run up to the
+ * launch and report
+ *   kernel | BN << 4 | splits << 16 | fast << 28 | persist << 29 | reduce << 30,   < 0: -hipError
+ * kernel: 0 gemm_generic (VALU), 1 gemm_mfma_bf16 (register-staged 128x128), 2 gemm_mfma_v2 (LDS-DMA
+ * 128x128), 3 gemm_8ph, 4 gemm_8pp, 5 gemm_4w, 6 gemm_8w; BN = tile width; splits = split-K slices (1: none);
+ * fast = gemm_8ph's full-tile variant; persist = a persistent grid; reduce: 0 none, 1 splitk_reduce (whole
+ * epilogue, any output type), 2 splitk_reduce_f32x4 (plain fp32).  uva_gemm_plan is unchanged. */
+long long uva_gemm_route(int in_dtype, int out_dtype, int ta, int tb, const void* A, const void* B, void* C, int M,
+                         int N, int K, long long lda, long long ldb, long long ldc, int batch, int batch_inner,
+                         long long sAo, long long sAi, long long sBo, long long sBi, long long sCo, long long sCi,
+                         const float* bias, const void* residual, long long ldr, long long sRo, long long sRi,
+                         void* aux, int act, float alpha, float beta, float drop_p, unsigned long long drop_seed,
+                         int res_dtype, const void* gate, long long ldg, int gate_dtype, int force_generic,
+                         float* workspace, long long ws_floats);
 /* Persistent 8-phase form (gemm_8pp: one workgroup per CU walks full tiles; the next tile's first
  * K-tiles are in flight under this tile's register epilogue) for eligible plain / bias / activation /
  * dropout products: 1 on, 0 off (default: measured 1-4 % slower than gemm_8ph),

@@ -1745,13 +1745,26 @@ __global__ __launch_bounds__(256) void splitk_reduce_f32x4(const float4* __restr
   }
 }
 
+// What a launcher decided (uva_gemm_route): with a non-null GemmRoute* the launchers below run their own
+// selection code up to the launch, record it here and return without launching anything.
+enum { RT_GENERIC = 0, RT_STAGED = 1, RT_DMA128 = 2, RT_8PH = 3, RT_8PP = 4, RT_4W = 5, RT_8W = 6 };
+struct GemmRoute {
+  int kernel, bn, splits, fast, persist, reduce;  // reduce: 0 none, 1 splitk_reduce, 2 splitk_reduce_f32x4
+};
+
+// the plain fp32 reduce on 16-byte lanes, else the scalar one with the whole epilogue
+template <typename TC>
+static bool reduce_is_f32x4(const float* part, const void* C, int N, long long ldc, const EpiParams& ep) {
+  const bool plain = !ep.bias && !ep.aux && !ep.residual && !ep.gate && ep.act == 0 && ep.drop_thresh == 0;
+  return sizeof(TC) == 4 && plain && N % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)C & 15) == 0 &&
+         ((uintptr_t)part & 15) == 0;
+}
+
 template <typename TC>
 static void launch_splitk_reduce(const float* part, int splits, void* C, int M, int N, long long ldc,
                                  const EpiParams& ep, hipStream_t s) {
   const long long n = (long long)M * N;
-  const bool plain = !ep.bias && !ep.aux && !ep.residual && !ep.gate && ep.act == 0 && ep.drop_thresh == 0;
-  if (sizeof(TC) == 4 && plain && N % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)C & 15) == 0 &&
-      ((uintptr_t)part & 15) == 0) {
+  if (reduce_is_f32x4<TC>(part, C, N, ldc, ep)) {
     const long long n4 = n / 4;
     long long blocks = (n4 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
@@ -1767,33 +1780,81 @@ static void launch_splitk_reduce(const float* part, int splits, void* C, int M, 
 // =====================================================================================
 // host launchers
 // =====================================================================================
-template <typename TI, typename TC>
-static int launch_generic(int ta, int tb, const void* A, const void* B, void* C, int M, int N, int K, long long lda,
-                          long long ldb, long long ldc, int batch, const BatchStrides& bs, const EpiParams& ep,
-                          const ConvParams& cp, hipStream_t s, float* ws = nullptr, long long ws_floats = 0) {
+// split-K slices (1 = none) and the K range of each
+struct SplitPlan {
+  int splits, kps;
+};
+
+// gemm_generic: the tiny-output long-K products
+static SplitPlan plan_generic(int ta, int M, int N, int K, int batch, bool have_ws, long long ws_floats) {
+  SplitPlan p{1, K};
   const long long nblk = (long long)((N + 63) / 64) * ((M + 63) / 64);
-  if (batch == 1 && ws && ta != 2 && nblk < 64 && K >= 4096) {
+  if (batch == 1 && have_ws && ta != 2 && nblk < 64 && K >= 4096) {
     // split K into slices of >= 256 so that ~512 blocks walk it; partial slabs in the workspace
     int splits = (int)((512 + nblk - 1) / nblk);
     if (splits > K / 256) splits = K / 256;
     while (splits > 1 && (long long)splits * M * N > ws_floats) --splits;
     if (splits > 1) {
-      const int kps = ((K + splits - 1) / splits + 15) / 16 * 16;
-      splits = (K + kps - 1) / kps;
-      dim3 sgrid((N + 63) / 64, (M + 63) / 64, splits);
+      p.kps = ((K + splits - 1) / splits + 15) / 16 * 16;
+      p.splits = (K + p.kps - 1) / p.kps;
+    }
+  }
+  return p;
+}
+
+// gemm_mfma_v2 / gemm_mfma_bf16 (128 x 128 tiles)
+static SplitPlan plan_mfma(int M, int N, int K, int batch, bool have_ws, long long ws_floats) {
+  const int nblk = ((M + MB_M - 1) / MB_M) * ((N + MB_N - 1) / MB_N);
+  // split-K when the output tiling cannot fill the chip (dW GEMMs: few tiles, K = tokens)
+  int splits = 1;
+  // K steps (x MB_K) per split, at least: 2 for the long-K training products; 4 for few-row GEMMs
+  // (M <= 1024: the inference sampler's 1024x1024 layers, 41 -> 34 ms per 100-step loop at B=32)
+  const int minks = M <= 1024 ? 4 : 2;
+  if (batch == 1 && have_ws && nblk < 256 && K >= 2 * minks * MB_K) {
+    splits = (512 + nblk - 1) / nblk;
+    int kmax = K / (minks * MB_K);
+    if (splits > kmax) splits = kmax;
+    // skinny outputs (the z_proj / DiffLoss input_proj dW, [768 | 1024] x 16 over K = tokens): the
+    // few 128x128 tiles need many more K slices to fill the chip (16 slices: 96 workgroups, 96 us for
+    // 100 MB of dY; the partial slabs stay small)
+    const int scap = (N <= 64 || M <= 64) ? 128 : 16;
+    if (splits > scap) splits = scap;
+    while (splits > 1 && (long long)splits * M * N > ws_floats) --splits;
+  }
+  SplitPlan p{splits, K};
+  if (splits > 1) {
+    p.kps = ((K + splits - 1) / splits + MB_K - 1) / MB_K * MB_K;
+    p.splits = (K + p.kps - 1) / p.kps;
+  }
+  return p;
+}
+
+template <typename TI, typename TC>
+static int launch_generic(int ta, int tb, const void* A, const void* B, void* C, int M, int N, int K, long long lda,
+                          long long ldb, long long ldc, int batch, const BatchStrides& bs, const EpiParams& ep,
+                          const ConvParams& cp, hipStream_t s, float* ws = nullptr, long long ws_floats = 0,
+                          GemmRoute* dry = nullptr) {
+  const SplitPlan sp = plan_generic(ta, M, N, K, batch, ws != nullptr, ws_floats);
+  if (dry) {
+    *dry = GemmRoute{RT_GENERIC, 64, sp.splits, 0, 0,
+                     sp.splits > 1 ? (reduce_is_f32x4<TC>(ws, C, N, ldc, ep) ? 2 : 1) : 0};
+    return 0;
+  }
+  if (sp.splits > 1) {
+    const int splits = sp.splits, kps = sp.kps;
+    dim3 sgrid((N + 63) / 64, (M + 63) / 64, splits);
 #define GS(a, b) gemm_generic<TI, TC, a, b, true><<<sgrid, 256, 0, s>>>((const TI*)A, (const TI*)B, (TC*)C, M, N, K, \
                                                                         lda, ldb, ldc, bs, ep, cp, ws, kps)
-      if (ta == 0 && tb == 0) GS(0, 0);
-      else if (ta == 0 && tb == 1) GS(0, 1);
-      else if (ta == 1 && tb == 0) GS(1, 0);
-      else if (ta == 1 && tb == 1) GS(1, 1);
-      else return (int)hipErrorInvalidValue;
+    if (ta == 0 && tb == 0) GS(0, 0);
+    else if (ta == 0 && tb == 1) GS(0, 1);
+    else if (ta == 1 && tb == 0) GS(1, 0);
+    else if (ta == 1 && tb == 1) GS(1, 1);
+    else return (int)hipErrorInvalidValue;
 #undef GS
-      UVA_LAUNCH_CHECK();
-      launch_splitk_reduce<TC>(ws, splits, C, M, N, ldc, ep, s);
-      UVA_LAUNCH_CHECK();
-      return 0;
-    }
+    UVA_LAUNCH_CHECK();
+    launch_splitk_reduce<TC>(ws, splits, C, M, N, ldc, ep, s);
+    UVA_LAUNCH_CHECK();
+    return 0;
   }
   dim3 grid((N + 63) / 64, (M + 63) / 64, batch);
 #define GG(a, b) gemm_generic<TI, TC, a, b><<<grid, 256, 0, s>>>((const TI*)A, (const TI*)B, (TC*)C, M, N, K, lda, ldb, ldc, bs, ep, cp)
@@ -1864,7 +1925,8 @@ static Plan8 plan_8ph(int ta, int M, int N, int K, int batch, bool gn_prologue, 
 template <typename TC>
 static int launch_8ph(int ta, int tb, const void* A, const void* B, void* C, int M, int N, int K, long long lda,
                       long long ldb, long long ldc, int batch, const BatchStrides& bs, const EpiParams& ep,
-                      const ConvParams& cp, float* ws, long long ws_floats, hipStream_t s) {
+                      const ConvParams& cp, float* ws, long long ws_floats, hipStream_t s,
+                      GemmRoute* dry = nullptr) {
   const Plan8 pl = plan_8ph(ta, M, N, K, batch, cp.gn_scale != nullptr, ws != nullptr, ws_floats);
   if (pl.bn == 0) return 0;
   const int bn = pl.bn, splits = pl.splits, kps = pl.kps;
@@ -1892,6 +1954,11 @@ static int launch_8ph(int ta, int tb, const void* A, const void* B, void* C, int
   const bool persist = g_gemm_persist && fast && splits == 1 && K >= 128 && ep.residual == nullptr &&
                        ep.gate == nullptr && ep.beta == 0.f && ep.res_grad == 0 && ldc % 8 == 0 &&
                        (((uintptr_t)C | (uintptr_t)ep.aux | (uintptr_t)ep.bias) % 16) == 0;
+  if (dry) {
+    *dry = GemmRoute{persist ? RT_8PP : RT_8PH, bn, splits, fast, persist,
+                     part ? (reduce_is_f32x4<TC>(part, C, N, ldc, ep) ? 2 : 1) : 0};
+    return 1;
+  }
   if (persist) {
     const unsigned g = (unsigned)std::min<long long>(nblk, (long long)ring_cus());
 #define G8P(a, b, BNV)                                                                                        do {                                                                                                          static bool attr = false;                                                                                   const int lb = Gemm8Cfg<BNV>::LDS_BYTES;                                                                    if (!attr) {                                                                                                  (void)hipFuncSetAttribute((const void*)gemm_8pp<a, b, BNV, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, lb);       attr = true;                                                                                              }                                                                                                           gemm_8pp<a, b, BNV, TC><<<dim3(g), 512, lb, s>>>((const bf16*)A, (const bf16*)B, (TC*)C, M, N, K, lda, ldb, ldc, ep);   } while (0)
@@ -1930,28 +1997,46 @@ static int launch_8ph(int ta, int tb, const void* A, const void* B, void* C, int
 template <typename TC>
 static int launch_mfma(int ta, int tb, const void* A, const void* B, void* C, int M, int N, int K, long long lda,
                        long long ldb, long long ldc, int batch, const BatchStrides& bs, const EpiParams& ep,
-                       const ConvParams& cp, float* ws, long long ws_floats, hipStream_t s) {
+                       const ConvParams& cp, float* ws, long long ws_floats, hipStream_t s,
+                       GemmRoute* dry = nullptr) {
   // K-contiguous products with a bias-only epilogue: the persistent 4-wave kernel (gemm4.hip)
   if (ta == 0 && tb == 0 && batch == 1 && !ep.residual && !ep.aux && !ep.gate && ep.act == 0 &&
       ep.drop_thresh == 0 && ep.beta == 0.f && ep.res_grad == 0) {
     // (the 8-wave kernel first when a measurement switch routes plain products to it)
     int r = uva_gemm8w_try(sizeof(TC) == 2 ? UVA_DT_BF16 : UVA_DT_F32, A, B, C, M, N, K, lda, ldb, ldc, ep.bias,
-                           ep.alpha, s);
+                           ep.alpha, s, dry != nullptr);
     if (r < 0) return -r;
-    if (r > 0) return 0;
+    if (r > 0) {
+      if (dry) *dry = GemmRoute{RT_8W, 192, 1, 0, 1, 0};
+      return 0;
+    }
     r = uva_gemm4_try(sizeof(TC) == 2 ? UVA_DT_BF16 : UVA_DT_F32, A, B, C, M, N, K, lda, ldb, ldc, ep.bias,
-                      ep.alpha, s);
+                      ep.alpha, s, dry != nullptr);
     if (r < 0) return -r;
-    if (r > 0) return 0;
+    if (r > 0) {
+      if (dry) *dry = GemmRoute{RT_4W, 192, 1, 0, 1, 0};
+      return 0;
+    }
   }
   // the dW products (M- / N-contiguous operands, fp32 gradients): the same kernel over split-K items
   if (sizeof(TC) == 4 && ta == 1 && tb == 1 && batch == 1 && !ep.bias && !ep.residual && !ep.aux && !ep.gate &&
       ep.act == 0 && ep.drop_thresh == 0 && ep.res_grad == 0) {
     int red = 0;
-    int r = uva_gemm8w_tt_try(A, B, (float*)C, M, N, K, lda, ldb, ldc, ep.alpha, ep.beta, ws, ws_floats, &red, s);
-    if (r == 0) r = uva_gemm4_tt_try(A, B, (float*)C, M, N, K, lda, ldb, ldc, ep.alpha, ep.beta, ws, ws_floats, &red, s);
+    int kern = RT_8W;
+    int r = uva_gemm8w_tt_try(A, B, (float*)C, M, N, K, lda, ldb, ldc, ep.alpha, ep.beta, ws, ws_floats, &red, s,
+                              dry != nullptr);
+    if (r == 0) {
+      kern = RT_4W;
+      r = uva_gemm4_tt_try(A, B, (float*)C, M, N, K, lda, ldb, ldc, ep.alpha, ep.beta, ws, ws_floats, &red, s,
+                           dry != nullptr);
+    }
     if (r < 0) return -r;
     if (r > 0) {
+      if (dry) {
+        *dry = GemmRoute{kern, 192, red > 0 ? red : 1, 0, 1,
+                         red > 0 ? (reduce_is_f32x4<TC>(ws, C, N, ldc, ep) ? 2 : 1) : 0};
+        return 0;
+      }
       if (red > 0) {
         launch_splitk_reduce<TC>(ws, red, C, M, N, ldc, ep, s);
         UVA_LAUNCH_CHECK();
@@ -1960,37 +2045,23 @@ static int launch_mfma(int ta, int tb, const void* A, const void* B, void* C, in
     }
   }
   {
-    int r = launch_8ph<TC>(ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, bs, ep, cp, ws, ws_floats, s);
+    int r = launch_8ph<TC>(ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, bs, ep, cp, ws, ws_floats, s, dry);
     if (r < 0) return -r;
     if (r > 0) return 0;
   }
   const int nblk = ((M + MB_M - 1) / MB_M) * ((N + MB_N - 1) / MB_N);
-  // split-K when the output tiling cannot fill the chip (dW GEMMs: few tiles, K = tokens)
-  int splits = 1;
-  // K steps (x MB_K) per split, at least: 2 for the long-K training products; 4 for few-row GEMMs
-  // (M <= 1024: the inference sampler's 1024x1024 layers, 41 -> 34 ms per 100-step loop at B=32)
-  const int minks = M <= 1024 ? 4 : 2;
-  if (batch == 1 && ws && nblk < 256 && K >= 2 * minks * MB_K) {
-    splits = (512 + nblk - 1) / nblk;
-    int kmax = K / (minks * MB_K);
-    if (splits > kmax) splits = kmax;
-    // skinny outputs (the z_proj / DiffLoss input_proj dW, [768 | 1024] x 16 over K = tokens): the
-    // few 128x128 tiles need many more K slices to fill the chip (16 slices: 96 workgroups, 96 us for
-    // 100 MB of dY; the partial slabs stay small)
-    const int scap = (N <= 64 || M <= 64) ? 128 : 16;
-    if (splits > scap) splits = scap;
-    while (splits > 1 && (long long)splits * M * N > ws_floats) --splits;
-  }
-  int kps = K;
-  if (splits > 1) {
-    kps = ((K + splits - 1) / splits + MB_K - 1) / MB_K * MB_K;
-    splits = (K + kps - 1) / kps;
-  }
+  const SplitPlan sp = plan_mfma(M, N, K, batch, ws != nullptr, ws_floats);
+  const int splits = sp.splits, kps = sp.kps;
   float* part = splits > 1 ? ws : nullptr;
   dim3 grid(nblk, splits, batch);
   // LDS-DMA needs 16-B aligned sources for every lane: K-contiguous lds/ld multiples of 8 (checked by
   // the dispatcher) -- and no register-side prologue (GN apply) on the A operand
   const bool v2 = !(ta == 2 && cp.gn_scale);
+  if (dry) {
+    *dry = GemmRoute{v2 ? RT_DMA128 : RT_STAGED, MB_N, splits, 0, 0,
+                     part ? (reduce_is_f32x4<TC>(part, C, N, ldc, ep) ? 2 : 1) : 0};
+    return 0;
+  }
   if (v2) {
     size_t lds2 = EPI_LDS_BYTES;  // >= 4 x 8192 bf16 staging images
     static bool attr2 = false;
@@ -2067,7 +2138,7 @@ static EpiParams make_epi(const float* bias, const void* residual, long long ldr
 static int gemm_dispatch(int in_dtype, int out_dtype, int ta, int tb, const void* A, const void* B, void* C, int M,
                          int N, int K, long long lda, long long ldb, long long ldc, int batch, const BatchStrides& bs,
                          const EpiParams& ep, const ConvParams& cp, int force_generic, float* ws, long long ws_floats,
-                         hipStream_t stream) {
+                         hipStream_t stream, GemmRoute* dry = nullptr) {
   if (in_dtype == UVA_DT_BF16) {
     // MFMA path needs 16-B chunks: K-contiguous dims and M/N-contiguous dims multiple of 8, aligned lds
     bool ok = !force_generic && (K % 8 == 0) && (((uintptr_t)A | (uintptr_t)B) % 16 == 0) &&
@@ -2077,30 +2148,31 @@ static int gemm_dispatch(int in_dtype, int out_dtype, int ta, int tb, const void
     else ok = ok && (lda % 8 == 0) && (!ta || M % 8 == 0);
     if (ok) {
       if (out_dtype == UVA_DT_BF16)
-        return launch_mfma<bf16>(ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, bs, ep, cp, ws, ws_floats, stream);
-      return launch_mfma<float>(ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, bs, ep, cp, ws, ws_floats, stream);
+        return launch_mfma<bf16>(ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, bs, ep, cp, ws, ws_floats, stream,
+                                 dry);
+      return launch_mfma<float>(ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, bs, ep, cp, ws, ws_floats, stream, dry);
     }
     if (out_dtype == UVA_DT_BF16)
       return launch_generic<bf16, bf16>(ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, bs, ep, cp, stream, ws,
-                                        ws_floats);
+                                        ws_floats, dry);
     return launch_generic<bf16, float>(ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, bs, ep, cp, stream, ws,
-                                       ws_floats);
+                                       ws_floats, dry);
   }
   if (out_dtype == UVA_DT_F32)
     return launch_generic<float, float>(ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, bs, ep, cp, stream, ws,
-                                        ws_floats);
+                                        ws_floats, dry);
   return launch_generic<float, bf16>(ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, bs, ep, cp, stream, ws,
-                                     ws_floats);
+                                     ws_floats, dry);
 }
 
-extern "C" int uva_gemm(int in_dtype, int out_dtype, int ta, int tb, const void* A, const void* B, void* C, int M,
-                        int N, int K, long long lda, long long ldb, long long ldc, int batch, int batch_inner,
-                        long long sAo, long long sAi, long long sBo, long long sBi, long long sCo, long long sCi,
-                        const float* bias, const void* residual, long long ldr, long long sRo, long long sRi,
-                        void* aux, int act, float alpha, float beta, float drop_p, unsigned long long drop_seed,
-                        int res_dtype, const void* gate, long long ldg, int gate_dtype, int force_generic,
-                        float* workspace, long long ws_floats, hipStream_t stream) {
-  if (M <= 0 || N <= 0 || batch <= 0 || K <= 0) return 0;
+static int gemm_entry(int in_dtype, int out_dtype, int ta, int tb, const void* A, const void* B, void* C, int M,
+                      int N, int K, long long lda, long long ldb, long long ldc, int batch, int batch_inner,
+                      long long sAo, long long sAi, long long sBo, long long sBi, long long sCo, long long sCi,
+                      const float* bias, const void* residual, long long ldr, long long sRo, long long sRi,
+                      void* aux, int act, float alpha, float beta, float drop_p, unsigned long long drop_seed,
+                      int res_dtype, const void* gate, long long ldg, int gate_dtype, int force_generic,
+                      float* workspace, long long ws_floats, hipStream_t stream, GemmRoute* dry) {
+  if (M <= 0 || N <= 0 || batch <= 0 || K <= 0) return dry ? (int)hipErrorInvalidValue : 0;
   if (ta == 2) return (int)hipErrorInvalidValue;  // conv view only through uva_conv2d
   BatchStrides bs{sAo, sAi, sBo, sBi, sCo, sCi, batch_inner > 0 ? batch_inner : 1};
   EpiParams ep = make_epi(bias, residual, ldr, sRo, sRi, aux, act, alpha, beta, drop_p, drop_seed);
@@ -2110,7 +2182,42 @@ extern "C" int uva_gemm(int in_dtype, int out_dtype, int ta, int tb, const void*
   ep.gate_dt = gate_dtype;
   ConvParams cp{};
   return gemm_dispatch(in_dtype, out_dtype, ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, bs, ep, cp, force_generic,
-                       workspace, ws_floats, stream);
+                       workspace, ws_floats, stream, dry);
+}
+
+extern "C" int uva_gemm(int in_dtype, int out_dtype, int ta, int tb, const void* A, const void* B, void* C, int M,
+                        int N, int K, long long lda, long long ldb, long long ldc, int batch, int batch_inner,
+                        long long sAo, long long sAi, long long sBo, long long sBi, long long sCo, long long sCi,
+                        const float* bias, const void* residual, long long ldr, long long sRo, long long sRi,
+                        void* aux, int act, float alpha, float beta, float drop_p, unsigned long long drop_seed,
+                        int res_dtype, const void* gate, long long ldg, int gate_dtype, int force_generic,
+                        float* workspace, long long ws_floats, hipStream_t stream) {
+  return gemm_entry(in_dtype, out_dtype, ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, batch_inner, sAo, sAi, sBo,
+                    sBi, sCo, sCi, bias, residual, ldr, sRo, sRi, aux, act, alpha, beta, drop_p, drop_seed, res_dtype,
+                    gate, ldg, gate_dtype, force_generic, workspace, ws_floats, stream, nullptr);
+}
+
+// The route uva_gemm takes for exactly these arguments (no device work, nothing launched): uva_gemm's own
+// dispatch and launchers run up to the launch and report
+//   kernel | BN << 4 | splits << 16 | fast << 28 | persist << 29 | reduce << 30,   < 0: -hipError
+// kernel: 0 gemm_generic, 1 gemm_mfma_bf16, 2 gemm_mfma_v2, 3 gemm_8ph, 4 gemm_8pp, 5 gemm_4w, 6 gemm_8w;
+// reduce: 0 none, 1 splitk_reduce, 2 splitk_reduce_f32x4.
+extern "C" long long uva_gemm_route(int in_dtype, int out_dtype, int ta, int tb, const void* A, const void* B,
+                                    void* C, int M, int N, int K, long long lda, long long ldb, long long ldc,
+                                    int batch, int batch_inner, long long sAo, long long sAi, long long sBo,
+                                    long long sBi, long long sCo, long long sCi, const float* bias,
+                                    const void* residual, long long ldr, long long sRo, long long sRi, void* aux,
+                                    int act, float alpha, float beta, float drop_p, unsigned long long drop_seed,
+                                    int res_dtype, const void* gate, long long ldg, int gate_dtype,
+                                    int force_generic, float* workspace, long long ws_floats) {
+  GemmRoute r{-1, 0, 0, 0, 0, 0};
+  const int rc = gemm_entry(in_dtype, out_dtype, ta, tb, A, B, C, M, N, K, lda, ldb, ldc, batch, batch_inner, sAo, sAi,
+                            sBo, sBi, sCo, sCi, bias, residual, ldr, sRo, sRi, aux, act, alpha, beta, drop_p,
+                            drop_seed, res_dtype, gate, ldg, gate_dtype, force_generic, workspace, ws_floats, nullptr,
+                            &r);
+  if (rc != 0 || r.kernel < 0) return -(long long)(rc != 0 ? rc : (int)hipErrorInvalidValue);
+  return (long long)r.kernel | ((long long)r.bn << 4) | ((long long)r.splits << 16) | ((long long)r.fast << 28) |
+         ((long long)r.persist << 29) | ((long long)r.reduce << 30);
 }
 
 extern "C" long long uva_gemm_plan(int in_dtype, int ta, int tb, int M, int N, int K, int batch, int gn_prologue,

@@ -369,7 +369,7 @@ static int g4_launch(const void* A, const void* B, void* C, int M, int N, int K,
 
 // 1 = launched, 0 = not eligible (caller falls back), < 0 = -hipError
 extern "C" int uva_gemm4_try(int out_dtype, const void* A, const void* B, void* C, int M, int N, int K, long long lda,
-                             long long ldb, long long ldc, const float* bias, float alpha, hipStream_t s) {
+                             long long ldb, long long ldc, const float* bias, float alpha, hipStream_t s, int dry) {
   if (!g_gemm4_on) return 0;
   if (M <= 0 || N <= 0 || K <= 0) return 0;
   if (lda % 8 || ldb % 8 || ldc % 8 || N % 8 || lda < K || ldb < K) return 0;
@@ -382,6 +382,7 @@ extern "C" int uva_gemm4_try(int out_dtype, const void* A, const void* B, void* 
   if (bias && ((uintptr_t)bias % 16)) return 0;
   const G4Choice c = g4_plan(M, N, K);
   if (c.cfg < 0) return 0;
+  if (dry) return 1;
   int r;
   if (out_dtype == UVA_DT_BF16) {
     r = g4_launch<8, 6, 0, 0, bf16>(A, B, C, M, N, K, lda, ldb, ldc, bias, alpha, c.grid, 1, K, 0, s);
@@ -402,12 +403,16 @@ static RingSplit g4_plan_tt(int M, int N, int K, long long ws_floats, bool need_
 // the dW products (return values: gemm_ring.h)
 extern "C" int uva_gemm4_tt_try(const void* A, const void* B, float* C, int M, int N, int K, long long lda,
                                 long long ldb, long long ldc, float alpha, float beta, float* ws, long long ws_floats,
-                                int* reduce, hipStream_t s) {
+                                int* reduce, hipStream_t s, int dry) {
   *reduce = 0;
   if (!g_gemm4_on) return 0;
   const RingSplit p = g4_plan_tt(M, N, K, ws ? ws_floats : 0, beta != 0.f);
   const bool direct = p.splits == 1 && beta == 0.f;
   if (!ring_tt_ok(A, B, C, ws, M, N, K, lda, ldb, ldc, p, direct)) return 0;
+  if (dry) {
+    if (!direct) *reduce = p.splits;
+    return 1;
+  }
   int r;
   if (direct) {
     r = g4_launch<8, 6, 1, 1, float>(A, B, C, M, N, K, lda, ldb, ldc, nullptr, alpha, p.grid, 1, K, 0, s);

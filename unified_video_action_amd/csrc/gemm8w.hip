@@ -662,13 +662,17 @@ static uint32_t g8_key(unsigned long long seed) { return drop_key(seed); }
 // the dW products on gemm_8w (mode bit 7: 128; return values: gemm_ring.h, 0 also when off)
 extern "C" int uva_gemm8w_tt_try(const void* A, const void* B, float* C, int M, int N, int K, long long lda,
                                  long long ldb, long long ldc, float alpha, float beta, float* ws, long long ws_floats,
-                                 int* reduce, hipStream_t s) {
+                                 int* reduce, hipStream_t s, int dry) {
   *reduce = 0;
   if (!(g_gemm8w_mode & 128)) return 0;
   // the shared split-K plan, any number of tiles
   const RingSplit p = ring_plan_tt(M, N, K, ws ? ws_floats : 0, beta != 0.f, LLONG_MAX);
   const bool direct = p.splits == 1 && beta == 0.f;
   if (!ring_tt_ok(A, B, C, ws, M, N, K, lda, ldb, ldc, p, direct)) return 0;
+  if (dry) {
+    if (!direct) *reduce = p.splits;
+    return 1;
+  }
   using G = G8Cfg<4, 6, 8>;
   static bool attr = false;
   if (!attr) {
@@ -688,9 +692,10 @@ extern "C" int uva_gemm8w_tt_try(const void* A, const void* B, float* C, int M, 
 
 // plain product (measurement route): 1 = launched, 0 = not eligible / off, < 0 = -hipError
 extern "C" int uva_gemm8w_try(int out_dtype, const void* A, const void* B, void* C, int M, int N, int K, long long lda,
-                              long long ldb, long long ldc, const float* bias, float alpha, hipStream_t s) {
+                              long long ldb, long long ldc, const float* bias, float alpha, hipStream_t s, int dry) {
   if (!g_gemm8w_on) return 0;
   if (!g8_ok(A, B, C, M, N, K, lda, ldb, ldc, out_dtype == UVA_DT_BF16 ? 2 : 4, bias)) return 0;
+  if (dry) return 1;
   G8Epi ep{bias, alpha, nullptr, nullptr, nullptr, nullptr, 0u, 0u, 1.f};
   const int r = out_dtype == UVA_DT_BF16
                     ? g8_dispatch<0, bf16>(A, B, C, M, N, K, (int)lda, (int)ldb, (int)ldc, ep, s)

@@ -184,14 +184,15 @@ static inline bool ring_tt_ok(const void* A, const void* B, const void* C, const
 
 // the ring kernels' entry points (called by gemm.hip's dispatch).  1 = launched, 0 = not eligible (the
 // caller falls back), < 0 = -hipError.  _tt_: *reduce = 0 -> C holds alpha * A^T B; *reduce = s > 0 -> ws
-// holds s fp32 partial slabs of M x N (ld N), the caller reduces them into C (alpha, beta)
+// holds s fp32 partial slabs of M x N (ld N), the caller reduces them into C (alpha, beta).
+// dry != 0 (uva_gemm_route): the same answer and *reduce, nothing launched
 extern "C" int uva_gemm4_try(int out_dtype, const void* A, const void* B, void* C, int M, int N, int K, long long lda,
-                             long long ldb, long long ldc, const float* bias, float alpha, hipStream_t s);
+                             long long ldb, long long ldc, const float* bias, float alpha, hipStream_t s, int dry);
 extern "C" int uva_gemm8w_try(int out_dtype, const void* A, const void* B, void* C, int M, int N, int K, long long lda,
-                              long long ldb, long long ldc, const float* bias, float alpha, hipStream_t s);
+                              long long ldb, long long ldc, const float* bias, float alpha, hipStream_t s, int dry);
 extern "C" int uva_gemm4_tt_try(const void* A, const void* B, float* C, int M, int N, int K, long long lda,
                                 long long ldb, long long ldc, float alpha, float beta, float* ws, long long ws_floats,
-                                int* reduce, hipStream_t s);
+                                int* reduce, hipStream_t s, int dry);
 extern "C" int uva_gemm8w_tt_try(const void* A, const void* B, float* C, int M, int N, int K, long long lda,
                                  long long ldb, long long ldc, float alpha, float beta, float* ws, long long ws_floats,
-                                 int* reduce, hipStream_t s);
+                                 int* reduce, hipStream_t s, int dry);

@@ -77,20 +77,45 @@ def _ld(t):
 def gemm(A, B, C, M, N, K, lda, ldb, ldc, ta=0, tb=0, batch=1, inner=1, sA=(0, 0), sB=(0, 0), sC=(0, 0),
          bias=None, residual=None, ldr=0, sR=(0, 0), aux=None, act="none", alpha=1.0, beta=0.0,
          drop_p=0.0, seed=0, force_generic=False, splitk=True, gate=None, ldg=0):
+    args = _gemm_args(A, B, C, M, N, K, lda, ldb, ldc, ta, tb, batch, inner, sA, sB, sC, bias, residual, ldr, sR, aux,
+                      act, alpha, beta, drop_p, seed, force_generic, splitk, gate, ldg)
+    with _traced(f"gemm[{'NT'[ta]}{'NT'[tb]}] {'bf16' if dt(A) else 'f32'} M{M} N{N} K{K} b{batch}",
+                 2.0 * M * N * K * batch):
+        _call("uva_gemm", *args, stream())
+
+
+def _gemm_args(A, B, C, M, N, K, lda, ldb, ldc, ta, tb, batch, inner, sA, sB, sC, bias, residual, ldr, sR, aux, act,
+               alpha, beta, drop_p, seed, force_generic, splitk, gate, ldg):
+    """uva_gemm's arguments up to the stream (shared by gemm and gemm_route)"""
     assert A.dtype == B.dtype, (A.dtype, B.dtype)
     ws = workspace(SPLITK_WS_FLOATS, A.device) if (splitk and batch == 1) else None
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.is_contiguous()
     if aux is not None:
         assert aux.dtype == C.dtype
-    with _traced(f"gemm[{'NT'[ta]}{'NT'[tb]}] {'bf16' if dt(A) else 'f32'} M{M} N{N} K{K} b{batch}",
-                 2.0 * M * N * K * batch):
-        _call("uva_gemm", dt(A), dt(C), ta, tb, ptr(A), ptr(B), ptr(C), M, N, K, lda, ldb, ldc, batch, inner,
-                   sA[0], sA[1], sB[0], sB[1], sC[0], sC[1], ptr(bias), ptr(residual), ldr, sR[0], sR[1], ptr(aux),
-                   ACT[act] if isinstance(act, str) else act, float(alpha), float(beta), float(drop_p),
-                   int(seed) & 0xFFFFFFFFFFFFFFFF, dt(residual) if residual is not None else 0, ptr(gate), ldg,
-                   dt(gate) if gate is not None else 0, int(force_generic), ptr(ws),
-                   ws.numel() if ws is not None else 0, stream())
+    return (dt(A), dt(C), ta, tb, ptr(A), ptr(B), ptr(C), M, N, K, lda, ldb, ldc, batch, inner,
+            sA[0], sA[1], sB[0], sB[1], sC[0], sC[1], ptr(bias), ptr(residual), ldr, sR[0], sR[1], ptr(aux),
+            ACT[act] if isinstance(act, str) else act, float(alpha), float(beta), float(drop_p),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, dt(residual) if residual is not None else 0, ptr(gate), ldg,
+            dt(gate) if gate is not None else 0, int(force_generic), ptr(ws), ws.numel() if ws is not None else 0)
+
+
+GEMM_KERNELS = ("generic", "staged", "dma128", "8ph", "8pp", "4w", "8w")
+GEMM_REDUCES = (None, "scalar", "f32x4")
+
+
+def gemm_route(A, B, C, M, N, K, lda, ldb, ldc, ta=0, tb=0, batch=1, inner=1, sA=(0, 0), sB=(0, 0), sC=(0, 0),
+               bias=None, residual=None, ldr=0, sR=(0, 0), aux=None, act="none", alpha=1.0, beta=0.0,
+               drop_p=0.0, seed=0, force_generic=False, splitk=True, gate=None, ldg=0):
+    """the route gemm() takes for exactly these arguments (uva_gemm_route; launches nothing) -> dict:
+    kernel (a GEMM_KERNELS name), bn, splits, fast, persist, reduce (a GEMM_REDUCES name)"""
+    code = lib().query("uva_gemm_route", *_gemm_args(A, B, C, M, N, K, lda, ldb, ldc, ta, tb, batch, inner, sA, sB,
+                                                     sC, bias, residual, ldr, sR, aux, act, alpha, beta, drop_p, seed,
+                                                     force_generic, splitk, gate, ldg))
+    if code < 0:
+        raise RuntimeError(f"uva_gemm_route failed with hipError {-code}")
+    return dict(kernel=GEMM_KERNELS[code & 15], bn=(code >> 4) & 4095, splits=(code >> 16) & 4095,
+                fast=bool((code >> 28) & 1), persist=bool((code >> 29) & 1), reduce=GEMM_REDUCES[(code >> 30) & 3])
 
 
 SPLITK_WS_FLOATS = 1 << 25  # 128 MB fp32 partial slabs
