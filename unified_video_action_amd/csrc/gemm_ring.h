@@ -29,11 +29,12 @@ struct RingCfg {
 // {8g + q} a 32-lane group of ds_read_b64_tr_b16 touches (32 B each) fall on 8 distinct 32-B bank
 // slots: 512-B rows (W = 256) all start on one bank -> XOR by 8 distinct even chunk offsets; 384-B rows
 // (W = 192) alternate between two bank halves -> 4 offsets within 128 B suffice (and keep the XOR
-// inside each 8-chunk group of the 24-chunk row)
+// inside each 8-chunk group of the 24-chunk row).  gemm.hip's half images take the same two: 256-B rows
+// (W = 128) as the 512-B rows, 128-B rows (W = 64) as the 384-B rows
 template <int W>
 __device__ __forceinline__ int ring_kswz(int k) {
-  static_assert(W == 256 || W == 192, "row width");
-  if constexpr (W == 256) return ((k & 3) << 1) | (((k >> 3) & 1) << 3);
+  static_assert(W == 256 || W == 192 || W == 128 || W == 64, "row width");
+  if constexpr (W == 256 || W == 128) return ((k & 3) << 1) | (((k >> 3) & 1) << 3);
   else return (((k >> 1) & 1) << 1) | (((k >> 3) & 1) << 2);
 }
 
