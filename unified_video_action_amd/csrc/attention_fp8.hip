@@ -1,8 +1,12 @@
 // FP8 (OCP e4m3) attention forward for the "fp8_attn" precision (BASELINE config 5, UMI-multi):
-// the same timm Attention / SDPA (mar_con_unified.py:201-249) with Q.K^T and P.V on the
-// block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 (e4m3 operands: twice the bf16 MFMA rate; the
-// non-scaled fp8 MFMAs run at the bf16 rate, MI355X_MICROARCH.md 'Matrix cores'), fp32
-// accumulation and fp32 online softmax.
+// the same timm Attention / SDPA (mar_con_unified.py:201-249) on e4m3 operands with P.V on the
+// block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 (twice the bf16 MFMA rate; the non-scaled fp8
+// MFMAs run at the bf16 rate, MI355X_MICROARCH.md 'Matrix cores') and an fp32 online softmax.
+// Q.K^T runs on v_mfma_f32_32x32x16_bf16 over the e4m3 codes (exact in bf16, fp32 accumulation):
+// the fp8 MFMAs, scaled or not, drop what lies 16 bits below the largest of their products
+// (2^16 + 1 -> 2^16), which on the scores moved the log-sum-exp by 3e-4 .. 4e-3 of a log2 and twice
+// as many probabilities across an e4m3 rounding boundary as tests/attn_ref.py allows (DESIGN
+// section 2).  On P.V the same loss stays below that file's (N + 64) 2^-24 term.
 //
 // Scaling: per (batch, head, q|k|v, 64-row tile) power-of-two scales 2^e with amax * 2^-e <= 448
 // (uva_attn_quant_fp8, one pass over the qkv GEMM output).  The same pass rounds the bf16 qkv
@@ -14,9 +18,9 @@
 //                         (32 keys of one d row, in the order the S accumulators pack them) is 32
 //                         contiguous bytes: position 32h + 16s + i holds key 32s + (i&3) + 8(i>>2) + 4h
 //   sc   [B, 3, H, N/64]  the fp32 scales 2^e.
-// The scales are the MFMAs' own e8m0 block scales (uniform per 64-row tile = per operand block),
-// so S and O come out of the matrix core already scaled: no per-element multiplies, no running
-// V-scale bookkeeping.
+// The V scale is the P.V MFMA's own e8m0 block scale (uniform per 64-key tile = per operand block),
+// so O comes out of the matrix core already scaled: no running V-scale bookkeeping.  The Q and K
+// scales multiply the softmax constant of the tile (one scalar product per tile).
 // Forward lane view (32x32 C/D map): S^T = K Q^T, a lane owns one query (lane & 31) and 16 keys
 // of each 32-key subtile; its 32 probabilities of a 64-key tile, packed to e4m3 in place, are the
 // B operand of O^T = V^T P^T.  Dropout reads the bf16 kernels' MQ bit plane (attention.hip): the
@@ -24,8 +28,7 @@
 // this lane view is a compile-time position + 16 (lane >> 5).
 // The row sums use the unrounded fp32 P, so the log-sum-exp matches an fp32 softmax of x~.
 #include "attention_frag.h"
-
-#define A8_MAX 448.0f
+#include "fp8_scale.h"
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;  // 32 e4m3 values: one lane's 32x32x64 operand
 
@@ -68,13 +71,8 @@ __global__ __launch_bounds__(256) void attn_quant_fp8_kernel(bf16* __restrict__ 
   if ((tid & 63) == 0) red[tid >> 6] = amax;
   __syncthreads();
   amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  // smallest e with amax * 2^-e <= 448 (e = 0 for an all-zero tile)
-  int e = 0;
-  if (amax > 0.f) {
-    e = (int)ceilf(log2f(amax / A8_MAX));
-    while (ldexpf(amax, -e) > A8_MAX) ++e;
-    while (ldexpf(amax, -(e - 1)) <= A8_MAX) --e;
-  }
+  // smallest e with amax * 2^-e <= 448, clamped to +-126 (e = 0 for an all-zero tile): fp8_scale.h
+  const int e = fp8_tile_exp(amax);
   const float inv = ldexpf(1.f, -e), s = ldexpf(1.f, e);
   int w[4];
 #pragma unroll
@@ -152,18 +150,30 @@ __device__ __forceinline__ i32x8 a8_frag32(const uint8_t* img, int r, int h) {
   return (i32x8){lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 }
 
+// 8 e4m3 bytes -> 8 bf16 (exact: 4 significant bits, exponents -9 .. 8)
+__device__ __forceinline__ bf16x8 a8_to_bf16(uint2 w) {
+  const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, true);
+  const auto c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, true);
+  return (bf16x8){(bf16)a[0], (bf16)a[1], (bf16)b[0], (bf16)b[1], (bf16)c[0], (bf16)c[1], (bf16)d[0], (bf16)d[1]};
+}
+
+// bf16 operand of 32x32x16 step j of row r of a 64-byte-row image: bytes [16 j + 8 h, +8) (chunk j, half h)
+__device__ __forceinline__ bf16x8 a8_frag8(const uint8_t* img, int r, int j, int h) {
+  return a8_to_bf16(*(const uint2*)(img + r * 64 + ((j ^ a8_swz<64>(r)) << 4) + 8 * h));
+}
+
 __device__ __forceinline__ int e8m0_of(float pow2) { return 127 + (int)__builtin_amdgcn_frexp_expf(pow2) - 1; }
 
 // =====================================================================================
-// forward: 4 waves x 32 queries per workgroup, 64-key tiles (one 32x32x64 MFMA per 32x32 score
-// tile, one per 32 d x 32 queries of P.V)
+// forward: 4 waves x 32 queries per workgroup, 64-key tiles (four 32x32x16 bf16 MFMAs per 32x32 score
+// tile, one 32x32x64 scaled fp8 MFMA per 32 d x 32 queries of P.V)
 // =====================================================================================
 template <bool DROP>
 __global__ __launch_bounds__(256, 2) void attn_fwd_fp8_kernel(const uint8_t* __restrict__ qk8,
                                                            const uint8_t* __restrict__ v8t,
                                                            const float* __restrict__ sc, bf16* __restrict__ out,
                                                            float* __restrict__ lse2, const uint64_t* __restrict__ MQ,
-                                                           int N, int H, float c, float dsc) {
+                                                           int N, int H, float cs, float dsc) {
   constexpr int KT = 64;
   // one LDS array (a second __shared__ object beside LDS-DMA targets can cost vmcnt(0) waits)
   __shared__ __attribute__((aligned(1024))) uint8_t smem[2 * 2 * KT * 64];
@@ -185,14 +195,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_fp8_kernel(const uint8_t* __r
   const int qrow = q0 + lq;
   const uint64_t* mq = DROP ? MQ + (long long)bh * nt64 * N : nullptr;  // [kv][q] words
 
-  // Q^T fragment (B operand of S^T = K Q^T): query qrow, d bytes [32 hh, +32)
-  i32x8 qf = {};
+  // Q^T fragments (B operands of S^T = K Q^T, four 32x32x16 bf16 steps): query qrow, d bytes [16 j + 8 hh, +8)
+  bf16x8 qf[4] = {};
   if (qrow < N) {
-    const int4 lo = *(const int4*)(Qg + (long long)qrow * ldq + 32 * hh);
-    const int4 hi = *(const int4*)(Qg + (long long)qrow * ldq + 32 * hh + 16);
-    qf = (i32x8){lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) qf[j] = a8_to_bf16(*(const uint2*)(Qg + (long long)qrow * ldq + 16 * j + 8 * hh));
   }
-  const int sq = e8m0_of(q0 < N ? sq_[q0 >> 6] : 1.f);  // the wave's 32 queries share one 64-row tile
+  const float cq = cs * (q0 < N ? sq_[q0 >> 6] : 1.f);  // the wave's 32 queries share one 64-row tile
   float m = -INFINITY, rs = 0.f;
   f32x16 o[2];
 #pragma unroll
@@ -213,13 +222,16 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_fp8_kernel(const uint8_t* __r
     }
     const uint8_t* cK = sK(cur);
     const uint8_t* cV = sV(cur);
-    const int sk = e8m0_of(sk_[kv]), sv = e8m0_of(sv_[kv]);
-    // S^T (32 keys x 32 queries) of the tile's two subtiles, already scaled by 2^(eq + ek)
+    const int sv = e8m0_of(sv_[kv]);
+    const float c = cq * sk_[kv];  // softmax constant times the tile's 2^(eq + ek): the codes' scores are unscaled
+    // S^T (32 keys x 32 queries) of the tile's two subtiles, on the codes
     f32x16 s[2];
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
-      const f32x16 z = {};
-      s[st] = mfma8s(a8_frag32(cK, st * 32 + lq, hh), qf, z, sk, sq);
+      s[st] = (f32x16){};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        s[st] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a8_frag8(cK, st * 32 + lq, j, hh), qf[j], s[st], 0, 0, 0);
     }
     float mx = __builtin_amdgcn_fmed3f(s[0][0], s[0][1], INFINITY);
 #pragma unroll

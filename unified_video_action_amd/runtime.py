@@ -9,8 +9,8 @@ class _Runtime:
     def __init__(self):
         self.compute_dtype = torch.bfloat16   # GEMM/attention operand dtype ("bf16" bench mode)
         self.flash_attention = True           # bf16 fused attention; False -> materialised GEMM+softmax
-        # "fp8_attn" precision: attention forward on fp8 (e4m3) MFMA with per-tile power-of-two
-        # scales, bf16 everywhere else (BASELINE config 5); backward = bf16 kernels on the fp8-rounded
+        # "fp8_attn" precision: attention forward on e4m3 operands with per-tile power-of-two scales
+        # (P.V on the scaled fp8 MFMA, Q.K^T on the bf16 MFMA over the e4m3 codes), bf16 everywhere else (BASELINE config 5); backward = bf16 kernels on the fp8-rounded
         # q / k / v (straight-through)
         self.attn_fp8 = False
         # VAE ResnetBlock: GroupNorm+SiLU applied inside the halo conv's input staging (True) or as
