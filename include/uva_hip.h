@@ -381,6 +381,33 @@ int uva_attn_bwd_hd(const void* qkv, const void* out, const void* dout, const fl
                     float* Dvec, void* dqkv, float* dbias, int accum, float* part, int B, int N, int H, int head_dim,
                     float scale, float drop_p, hipStream_t stream);
 
+/* ---- CLIP text tower, forward only (csrc/text_tower.hip; utils/language_model.py:7-33 ->
+ *      transformers CLIPTextTransformer, run inside the step by policy:241-252 and :366-378).
+ *      ViT-B/32 text side: width D = 512, H = 8 heads of 64, causal, QuickGELU, context L <= 77.  LayerNorms
+ *      and Linears of a layer run on uva_layernorm_fwd / uva_gemm; these four are the rest.
+ * uva_clip_embed: x[b L + t][:] = tok_emb[ids[b][t]][:] + pos_emb[t][:], fp32 [B L][D] (the residual stream).
+ *      ids: int64 (ids_i64 = 1) or int32 (0) on the device.  The row index is clamped to [0, vocab - 1] inside
+ *      the kernel: a corrupt id reads a wrong row, never out of bounds.  D % 4 == 0, 16-B aligned tables.
+ * uva_clip_attn: out[B L][H 64] = softmax(scale Q K^T + causal + keymask) V on qkv [B L][3][H][64] (the qkv
+ *      GEMM's output, in place).  key_mask [B][L] integers (mask_i64 as ids_i64; NULL = all ones): key j serves
+ *      query i iff j <= i and key_mask[b][j] != 0.  A masked or padded key contributes exactly 0 (its score is
+ *      a large finite negative, never -inf).  dtype bf16: v_mfma_f32_16x16x32_bf16 on LDS-staged Q / K / V, L
+ *      padded to the MFMA tile inside the kernel, fp32 softmax; dtype fp32 (the parity route): VALU dot
+ *      products on fp32 qkv, fp32 out.  One workgroup per (batch, head).  1 <= L <= 77, else
+ *      hipErrorInvalidValue.  PRECONDITION: key_mask[b][0] != 0 for every b (position 0 is BOS, so no query row
+ *      is empty); the Python host checks it for a host-resident mask.  A row that breaks it stores zeros.
+ * uva_quick_gelu: y = x * sigmoid(1.702 x) over n contiguous elements, bf16 or fp32 in and out (CLIPMLP's
+ *      activation); 16-B aligned, any n (scalar tail for n % 8).
+ * uva_clip_pool: out[b][:] = x[b L + argmax_t ids[b][t]][:] (first maximum: CLIPTextTransformer's EOT pooling),
+ *      fp32 [B][D]; index (nullable) receives the B positions.  The index never leaves the device. */
+int uva_clip_embed(const void* ids, int ids_i64, const float* tok_emb, const float* pos_emb, float* x, int B, int L,
+                   int D, int vocab, hipStream_t stream);
+int uva_clip_attn(int dtype, const void* qkv, const void* key_mask, int mask_i64, void* out, int B, int L, int H,
+                  float scale, hipStream_t stream);
+int uva_quick_gelu(int dtype, const void* x, void* y, long long n, hipStream_t stream);
+int uva_clip_pool(const void* ids, int ids_i64, const float* x, float* out, int* index, int B, int L, int D,
+                  hipStream_t stream);
+
 /* ---- KL-VAE encoder plumbing (vae/vaekl.py, utils/data_utils.py) ---------------------
  * uva_resize_select: obs image [B,T,3,Hin,Win] fp32 in [0,1] -> NHWC [B*nsel,256,256,Cpad]
  *   frames sel[] (select_frames, data_utils.py:140-158), bilinear align_corners=False

@@ -746,3 +746,81 @@ def upsample_nearest2x(x, y):
     if not (x.is_contiguous() and y.is_contiguous() and y.shape == (n, 2 * H, 2 * W, C) and y.dtype == x.dtype):
         raise ValueError(f"upsample_nearest2x: {tuple(x.shape)} -> {tuple(y.shape)}")
     _call("uva_upsample_nearest2x", dt(x), ptr(x), ptr(y), n, H, W, C, stream())
+
+
+# ---- CLIP text tower (csrc/text_tower.hip; forward only) ------------------------------------------------
+CLIP_MAX_L = 77
+
+
+def _int_code(t, what):
+    """ids_i64 / mask_i64 of an integer device tensor (int64 -> 1, int32 -> 0)"""
+    if t.dtype == torch.int64:
+        return 1
+    if t.dtype == torch.int32:
+        return 0
+    raise TypeError(f"{what}: int64 or int32 expected, got {t.dtype}")
+
+
+def clip_embed(ids, tok_emb, pos_emb, x):
+    """x [B L, D] fp32 = tok_emb[ids] + pos_emb[:L] (uva_clip_embed).  The kernel clamps every id to
+    [0, vocab - 1], so a corrupt id reads a wrong row and never out of bounds."""
+    B, L = ids.shape
+    vocab, D = tok_emb.shape
+    if not (ids.is_contiguous() and tok_emb.is_contiguous() and pos_emb.is_contiguous() and x.is_contiguous()):
+        raise ValueError("clip_embed: contiguous tensors expected")
+    if not (ids.device == tok_emb.device == pos_emb.device == x.device):
+        raise ValueError("clip_embed: ids, tables and output must be on one device")
+    if not (tok_emb.dtype == pos_emb.dtype == x.dtype == torch.float32):
+        raise TypeError("clip_embed: fp32 tables and output expected")
+    if pos_emb.shape[0] < L or pos_emb.shape[1] != D or tuple(x.shape) != (B * L, D):
+        raise ValueError(f"clip_embed: ids {tuple(ids.shape)}, pos {tuple(pos_emb.shape)}, x {tuple(x.shape)}")
+    _call("uva_clip_embed", ptr(ids), _int_code(ids, "clip_embed ids"), ptr(tok_emb), ptr(pos_emb), ptr(x), B, L, D,
+          vocab, stream())
+
+
+def clip_attn(qkv, key_mask, out, B, L, H, scale=64 ** -0.5):
+    """out [B L, H 64] = causal, key-masked attention on qkv [B L, 3 H 64] (uva_clip_attn); bf16 in -> bf16
+    out (MFMA), fp32 in -> fp32 out (the parity route).  key_mask [B, L] int64 / int32 on the device, or None.
+    Position 0 must be kept in every row (BOS); the caller checks a host-resident mask, see clip_check_mask."""
+    if not 1 <= L <= CLIP_MAX_L:
+        raise ValueError(f"clip_attn: L = {L} outside 1..{CLIP_MAX_L}")
+    if tuple(qkv.shape) != (B * L, 3 * H * 64) or tuple(out.shape) != (B * L, H * 64):
+        raise ValueError(f"clip_attn: qkv {tuple(qkv.shape)} / out {tuple(out.shape)} for B {B} L {L} H {H}")
+    if not (qkv.is_contiguous() and out.is_contiguous() and qkv.dtype == out.dtype):
+        raise ValueError("clip_attn: contiguous qkv / out of one dtype expected")
+    mi = 0
+    if key_mask is not None:
+        if tuple(key_mask.shape) != (B, L) or not key_mask.is_contiguous() or key_mask.device != qkv.device:
+            raise ValueError(f"clip_attn: key_mask {tuple(key_mask.shape)} on {key_mask.device} for B {B} L {L} "
+                             f"on {qkv.device}")
+        mi = _int_code(key_mask, "clip_attn key_mask")
+    _call("uva_clip_attn", dt(qkv), ptr(qkv), ptr(key_mask), mi, ptr(out), B, L, H, float(scale), stream())
+
+
+def clip_check_mask(mask):
+    """the attention precondition on a HOST-resident mask: position 0 (BOS) is kept in every row.  A device
+    mask is not read back (no sync on the step's path); the kernel stores zeros for a row that breaks it."""
+    if mask is not None and mask.device.type == "cpu" and not bool((mask[:, 0] != 0).all()):
+        raise ValueError("CLIP attention mask: position 0 (BOS) must be 1 in every row")
+
+
+def quick_gelu(x, y):
+    """y = x * sigmoid(1.702 x), bf16 or fp32, any element count (uva_quick_gelu)"""
+    if not (x.is_contiguous() and y.is_contiguous() and x.dtype == y.dtype and x.shape == y.shape):
+        raise ValueError("quick_gelu: contiguous x / y of one dtype and shape expected")
+    if x.numel():
+        _call("uva_quick_gelu", dt(x), ptr(x), ptr(y), x.numel(), stream())
+
+
+def clip_pool(ids, x, out, index=None):
+    """out [B, D] = x [B L, D] rows at the first maximum of ids[b, :] (uva_clip_pool); index: optional int32
+    [B] receiving the positions.  The position is computed and used on the device."""
+    B, L = ids.shape
+    D = x.shape[1]
+    if not (ids.is_contiguous() and x.is_contiguous() and out.is_contiguous() and ids.device == x.device == out.device):
+        raise ValueError("clip_pool: contiguous tensors on one device expected")
+    if not (x.dtype == out.dtype == torch.float32) or tuple(x.shape) != (B * L, D) or tuple(out.shape) != (B, D):
+        raise ValueError(f"clip_pool: ids {tuple(ids.shape)}, x {tuple(x.shape)} {x.dtype}, out {tuple(out.shape)}")
+    if index is not None and not (index.dtype == torch.int32 and index.numel() == B and index.is_contiguous()):
+        raise ValueError("clip_pool: index must be contiguous int32 [B]")
+    _call("uva_clip_pool", ptr(ids), _int_code(ids, "clip_pool ids"), ptr(x), ptr(out), ptr(index), B, L, D, stream())

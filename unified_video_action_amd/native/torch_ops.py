@@ -24,6 +24,9 @@ without a GPU) and for op-level parity tests (tests/test_torch_ops_cpu.py, tests
   uva::conv3x3(x, weight, bias?, gn_scale?, gn_shift?, residual?) -> y
       KL-VAE ResnetBlock conv over NHWC bf16 with the GroupNorm-apply + SiLU prologue and the residual
       add fused (vaekl.py:56-113); forward only (the VAE is frozen on the training path).
+  uva::clip_attention(qkv, key_mask?, heads) -> out  and  uva::quick_gelu(x) -> y
+      the CLIP text tower's causal, key-masked attention (L <= 77) and CLIPMLP's activation
+      (utils/language_model.py; transformers CLIPAttention / quick_gelu); forward only (the tower is frozen).
 Backward ops: uva::layer_norm_backward, uva::linear_backward, uva::attention_backward.
 Dropout masks are the library's counter hash of (seed, element): the backward regenerates the
 forward's mask from the same seed.
@@ -324,3 +327,47 @@ def conv3x3(x: Tensor, weight: Tensor, bias: Optional[Tensor], gn_scale: Optiona
 def _conv3x3_fake(x, weight, bias, gn_scale, gn_shift, residual):
     n, H, W, _ = x.shape
     return x.new_empty(n, H, W, weight.shape[0])
+
+
+# ---- CLIP text tower ops (forward only: the tower is frozen, no autograd registration) ---------
+def _clip_attn_dims(qkv: Tensor, key_mask: Optional[Tensor], heads: int):
+    if qkv.dim() != 3 or qkv.shape[-1] != 3 * heads * 64:
+        raise ValueError(f"uva::clip_attention: qkv must be [B, L, 3*heads*64], got {tuple(qkv.shape)} for {heads} heads")
+    B, L = qkv.shape[0], qkv.shape[1]
+    if not 1 <= L <= ops.CLIP_MAX_L:
+        raise ValueError(f"uva::clip_attention: L = {L} outside 1..{ops.CLIP_MAX_L}")
+    if key_mask is not None and tuple(key_mask.shape) != (B, L):
+        raise ValueError(f"uva::clip_attention: key_mask must be [B, L] = {(B, L)}, got {tuple(key_mask.shape)}")
+    return B, L
+
+
+@torch.library.custom_op("uva::clip_attention", mutates_args=(), device_types="cuda")
+def clip_attention(qkv: Tensor, key_mask: Optional[Tensor], heads: int) -> Tensor:
+    """causal self-attention with a key mask of the CLIP text tower (CLIPAttention, head_dim 64): qkv
+    [B, L, 3*heads*64] bf16 (MFMA) or fp32 (parity route), key_mask [B, L] int64 / int32 (1 = keep; position
+    0 kept in every row) or None -> [B, L, heads*64] in qkv's dtype."""
+    B, L = _clip_attn_dims(qkv, key_mask, heads)
+    q = qkv.contiguous().view(B * L, -1)
+    out = torch.empty(B * L, heads * 64, dtype=qkv.dtype, device=qkv.device)
+    ops.clip_attn(q, None if key_mask is None else key_mask.contiguous(), out, B, L, heads)
+    return out.view(B, L, heads * 64)
+
+
+@clip_attention.register_fake
+def _clip_attention_fake(qkv, key_mask, heads):
+    B, L = _clip_attn_dims(qkv, key_mask, heads)
+    return qkv.new_empty(B, L, heads * 64)
+
+
+@torch.library.custom_op("uva::quick_gelu", mutates_args=(), device_types="cuda")
+def quick_gelu(x: Tensor) -> Tensor:
+    """x * sigmoid(1.702 x) (CLIPMLP's activation), bf16 or fp32"""
+    xc = x.contiguous()
+    y = torch.empty_like(xc)
+    ops.quick_gelu(xc, y)
+    return y
+
+
+@quick_gelu.register_fake
+def _quick_gelu_fake(x):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)

@@ -67,6 +67,13 @@ def _add_anchor(module, state_dict, prefix, local_metadata, strict, missing_keys
     state_dict.setdefault(prefix + "ddp_anchor", torch.zeros((), device=module.ddp_anchor.device))
 
 
+def _add_text_model(module, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+    """a checkpoint written without the (frozen, pretrained) text tower loads into a policy that has one"""
+    if module.text_model is not None:
+        for k, v in module.text_model.state_dict().items():
+            state_dict.setdefault(prefix + "text_model." + k, v)
+
+
 def _after_load(module, incompatible_keys):
     """loaded weights went into the flat fp32 buffer in place: refresh its bf16 compute shadow."""
     opt = module.bound_optimizer()
@@ -129,6 +136,15 @@ class UnifiedVideoActionPolicy(nn.Module):
             predict_proprioception=kwargs.get("predict_proprioception") or False, task_name=self.task_name,
             language_emb_model=language_emb_model, shape_meta=shape_meta)
         self.normalizer = LinearNormalizer()
+        # CLIP text tower (policy:72-74 get_text_model): built only from a local HF CLIP directory given as
+        # model.policy.language_model_path; frozen, outside self.model (so outside the optimizer's groups, the
+        # flat ParamStore and the DP buckets).  Without the path callers pass precomputed latents.
+        self.text_model, self.tokenizer, self.max_length = None, None, 30
+        if language_emb_model == "clip" and kwargs.get("language_model_path"):
+            from ..utils.language_model import get_text_model
+            self.text_model, self.tokenizer, self.max_length = get_text_model(
+                self.task_name, language_emb_model, kwargs["language_model_path"])
+        self._register_load_state_dict_pre_hook(_add_text_model, with_module=True)
         # DDP anchor (see module docstring); not part of state dicts
         self.ddp_anchor = nn.Parameter(torch.zeros(()))
         self._register_state_dict_hook(_drop_anchor)
@@ -221,14 +237,41 @@ class UnifiedVideoActionPolicy(nn.Module):
                                   "unexpected": list(unexpected)}
         return self.pretrained_report
 
+    def _encode_tokens(self, input_ids, attention_mask, dev):
+        """extract_text_features (language_model.py:25-33) on the HIP tower -> [B, 512] fp32"""
+        mask = None if attention_mask is None else attention_mask.to(dev)
+        return self.text_model(input_ids.to(dev), mask)
+
+    def _goal_latents(self, language_goal, dev):
+        """predict_action's language_goal with a text tower (policy:241-252): an integer token tensor
+        [B, 2, L] (input_ids, attention_mask -- one step of the dataset's obs["language"]), a dict with
+        input_ids / attention_mask, or a str / list of str when a tokenizer exists.  None: not tokens."""
+        if torch.is_tensor(language_goal) and not language_goal.is_floating_point():
+            if language_goal.dim() != 3 or language_goal.shape[1] != 2:
+                raise ValueError(f"language_goal tokens must be [B, 2, L], got {tuple(language_goal.shape)}")
+            return self._encode_tokens(language_goal[:, 0].long(), language_goal[:, 1].long(), dev)
+        if isinstance(language_goal, str) or (isinstance(language_goal, (list, tuple)) and language_goal
+                                              and all(isinstance(g, str) for g in language_goal)):
+            if self.tokenizer is None:
+                raise NotImplementedError("a text language_goal needs a tokenizer (the transformers package and "
+                                          "tokenizer files in language_model_path); pass tokens or latents")
+            language_goal = self.tokenizer(language_goal, padding="max_length", max_length=self.max_length,
+                                           return_tensors="pt")
+        if hasattr(language_goal, "keys") and "input_ids" in language_goal:
+            ids = torch.as_tensor(language_goal["input_ids"]).long()
+            mask = language_goal.get("attention_mask")
+            return self._encode_tokens(ids, None if mask is None else torch.as_tensor(mask).long(), dev)
+        return None
+
     def _normalize(self, key, x):
         if self.normalizer_type == "all" and key in self.normalizer:
             return self.normalizer[key].normalize(x)
         return x
 
     def compute_loss(self, batch, rng=None):
-        """batch: {"obs": {<image key>: [B,T,3,H,W] in [0,1] (any H), low-dim keys...},
-        "action": [B,T,Da], optional "language_latents": [B,512]}.  `rng` injects the step's
+        """batch: {"obs": {<image key>: [B,T,3,H,W] in [0,1] (any H), low-dim keys..., optional
+        "language": [B,T,2,L] integer tokens when the policy has a text tower}, "action": [B,T,Da],
+        optional "language_latents": [B,512]}.  `rng` injects the step's
         random draws (cases.py semantics) for parity runs."""
         rng = rng or {}
         obs = batch["obs"]
@@ -237,9 +280,19 @@ class UnifiedVideoActionPolicy(nn.Module):
         dev = img.device
         text_latents = None
         if self.language_emb_model == "clip":
-            if "language_latents" not in batch:
+            if self.text_model is not None and "language" in obs:
+                # policy:366-378: the dataset's [B, T, 2, L] tokens (libero_replay_image_dataset.py:344-415),
+                # first step: input_ids, attention_mask
+                language = obs["language"]
+                obs = {k: v for k, v in obs.items() if k != "language"}
+                if language.is_floating_point() or language.dim() != 4 or language.shape[2] != 2:
+                    raise ValueError(f"obs['language'] must be integer tokens [B, T, 2, L], got {language.dtype} "
+                                     f"{tuple(language.shape)}")
+                text_latents = self._encode_tokens(language[:, 0, 0].long(), language[:, 0, 1].long(), dev)
+            elif "language_latents" not in batch:
                 raise NotImplementedError("CLIP text encoding needs network weights; pass language_latents")
-            text_latents = batch["language_latents"]
+            else:
+                text_latents = batch["language_latents"]
         nactions = self._normalize("action", batch["action"].float())
         if self.normalizer_type == "all":  # normalize_obs: every non-image key (policy:389-393)
             obs = dict(obs)
@@ -338,7 +391,8 @@ class UnifiedVideoActionPolicy(nn.Module):
     def predict_action(self, obs_dict, language_goal=None, rng=None):
         """obs_dict: {"image" (or the task's camera key): [B,T,3,H,W] in [0,1], low-dim keys}
         -> {"action": [B, n_action_steps, Da], "action_pred": [B, 16, Da]}  (policy:221-320).
-        language_goal: precomputed text latents [B, 512] (CLIP needs network weights).
+        language_goal: precomputed text latents [B, 512] (float); with a text tower (language_model_path)
+        also integer tokens [B, 2, L], {"input_ids", "attention_mask"} or, given a tokenizer, text.
         rng injects {"vae_eps": [B*4,16,16,16] (posterior.sample, reference (b t) order),
         "noise", "step_noise"} for parity runs."""
         rng = rng or {}
@@ -354,9 +408,12 @@ class UnifiedVideoActionPolicy(nn.Module):
         dev = img.device
         text_latents = None
         if self.language_emb_model == "clip":
-            if not torch.is_tensor(language_goal):
-                raise NotImplementedError("CLIP text encoding needs network weights; pass text latents [B, 512]")
-            text_latents = language_goal.to(dev).float()
+            if self.text_model is not None:
+                text_latents = self._goal_latents(language_goal, dev)
+            if text_latents is None:
+                if not torch.is_tensor(language_goal):
+                    raise NotImplementedError("CLIP text encoding needs network weights; pass text latents [B, 512]")
+                text_latents = language_goal.to(dev).float()
         if self.normalizer_type == "all":  # normalize_obs: every non-image key (data_utils.py:185-203)
             for k in list(obs):
                 if "image" not in k and k in self.normalizer:
