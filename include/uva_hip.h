@@ -288,7 +288,13 @@ int uva_p_sample_step(int odt, const void* out, long long ld_out, const float* x
  *         (lnw/lnb nullable; shift/scale bf16 columns of the adaLN modulation, row stride ldm).
  * ln = 0: A' = A bf16 [R, lda].  act: 0 or 2 (SiLU).  gate/res (both or neither, fp32 out):
  * out = res + gate * v.  Supported: (ln, SiLU, bf16 out), (ln, none, fp32 out),
- * (plain, gate, fp32 out), (plain, SiLU, bf16 out). */
+ * (plain, gate, fp32 out), (plain, SiLU, bf16 out).  Refused (hipErrorInvalidValue, nothing launched):
+ * any other combination, lda / ldm off the vector width (ln: multiples of 4, plain: lda a multiple of 8),
+ * A / W / lnw / lnb not 16-byte aligned, shift / scale not 8-byte aligned, lnw without lnb.
+ * uva_sampler_linear_route: the tiling the launcher takes for (R, N, K) -- 0 the 32 x 64 tiles (4 waves,
+ * each over the full K), 1 the narrow 32 x 16 tiles (8 waves split K; taken when ceil(R/32) * ceil(N/64)
+ * < 64), -1 for a refused shape.  Pure host. */
+int uva_sampler_linear_route(int R, int N, int K);
 int uva_sampler_linear(int ln, const void* A, long long lda, const float* lnw, const float* lnb, const void* shift,
                        const void* scale, long long ldm, float eps, const void* W, const float* bias, int act,
                        const void* gate, long long ldg, const float* res, long long ldr, int odt, void* out,
@@ -306,7 +312,15 @@ int uva_sampler_linear(int ln, const void* A, long long lda, const float* lnw, c
  * C <= 16.  A run in which any hand-off wait hit its spin bound writes NaN to every x_out element and
  * sets the give-up flag; uva_sampler_persistent_status reads that flag (0 = clean; syncs the stream).
  * The 64 workgroups must be co-resident (one per CU): callers check the CU count first.
- * uva_sampler_persistent_test_hook(1): the NEXT launch publishes no phase (tests of the give-up path). */
+ * uva_sampler_persistent_test_hook(1): the NEXT launch publishes no phase (tests of the give-up path).
+ * Layout of work (a contract: tests read the exchange buffers back after a launch), byte offsets:
+ *     0  unsigned cnt[2 depth]  arrival counters (fc1 of block i at 2i, fc2 at 2i + 1)
+ *   128  unsigned flag          give-up flag (word 32)
+ *   256  float hx[2][16][W]     residual stream, ping-pong: block i writes side i & 1, so after a launch
+ *                               side (depth - 1) & 1 holds the last step's last block output (rows < R)
+ *   256 + 2 * 16 * W * 4  bf16 ha[16][W]   fc1 output of the last step's last block (all 16 rows; rows
+ *                               >= R are SiLU(b1))
+ * uva_sampler_persistent_workspace(W) = 256 + 2 * 16 * W * 4 + 16 * W * 2. */
 long long uva_sampler_persistent_workspace(int W);
 int uva_sampler_persistent(int R, int C, int W, int depth, int S, int clip, float eps, const void* w1, const float* b1,
                            const void* w2, const float* b2, const float* lnw, const float* lnb, const void* win,

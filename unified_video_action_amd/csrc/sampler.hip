@@ -172,6 +172,18 @@ __global__ __launch_bounds__(NARROW ? 512 : 256) void sampler_linear_kernel(
 }
 }  // namespace
 
+// the tiling uva_sampler_linear takes: the 32 x 64 tile grid, or (under 64 workgroups) the narrow 32 x 16
+// tiles with K split over 8 waves -- the launcher and the route query share this one expression
+static inline bool sl_narrow(int R, int N) {
+  const long long mb = (R + SL_BM - 1) / SL_BM;
+  return mb * ((N + SL_BN - 1) / SL_BN) < 64;
+}
+
+extern "C" int uva_sampler_linear_route(int R, int N, int K) {
+  if (R <= 0 || N <= 0 || (K != 1024 && K != 512 && K != 256)) return -1;
+  return sl_narrow(R, N) ? 1 : 0;
+}
+
 extern "C" int uva_sampler_linear(int ln, const void* A, long long lda, const float* lnw, const float* lnb,
                                   const void* shift, const void* scale, long long ldm, float eps, const void* W,
                                   const float* bias, int act, const void* gate, long long ldg, const float* res,
@@ -183,9 +195,14 @@ extern "C" int uva_sampler_linear(int ln, const void* A, long long lda, const fl
   if ((gate == nullptr) != (res == nullptr) || (ln && (!shift || !scale)) || (act != 0 && act != ACT_SILU)) {
     return (int)hipErrorInvalidValue;
   }
-  // the 32 x 64 tile grid, or (under 64 workgroups) the narrow 32 x 16 tiles with K split over 8 waves
+  // vector loads: X rows / lnw / lnb / W / bf16 A rows as 16-byte vectors, shift / scale as 8-byte vectors
+  if (!A || !W || (((uintptr_t)A | (uintptr_t)W) & 15) ||
+      (ln && ((((uintptr_t)lnw | (uintptr_t)lnb) & 15) || (((uintptr_t)shift | (uintptr_t)scale) & 7))) ||
+      (ln && (lnw == nullptr) != (lnb == nullptr))) {
+    return (int)hipErrorInvalidValue;
+  }
   const unsigned mb = (unsigned)((R + SL_BM - 1) / SL_BM);
-  const bool narrow = (long long)mb * ((N + SL_BN - 1) / SL_BN) < 64;
+  const bool narrow = sl_narrow(R, N);
   const dim3 grid(mb, (unsigned)(narrow ? (N + 15) / 16 : (N + SL_BN - 1) / SL_BN));
 #define SLKK(L, AC, G, T, KSV)                                                                                    \
   do {                                                                                                            \

@@ -487,6 +487,15 @@ def sampler_linear(A, W, out, bias=None, act="none", ln=False, lnw=None, lnb=Non
                out.stride(0), R, N, K, stream())
 
 
+def sampler_linear_route(R, N, K):
+    """the tiling uva_sampler_linear takes for (R, N, K): "narrow" (32 x 16 tiles, 8 waves split K) or
+    "wide" (32 x 64 tiles); pure host"""
+    r = lib().query("uva_sampler_linear_route", R, N, K)
+    if r < 0:
+        raise ValueError(f"sampler_linear_route: refused shape R {R} N {N} K {K}")
+    return "narrow" if r else "wide"
+
+
 def weighted_mean(l, w, res):
     _call("uva_weighted_mean", ptr(l), ptr(w), l.numel(), ptr(res), stream())
 
