@@ -422,6 +422,51 @@ int uva_quick_gelu(int dtype, const void* x, void* y, long long n, hipStream_t s
 int uva_clip_pool(const void* ids, int ids_i64, const float* x, float* out, int* index, int B, int L, int D,
                   hipStream_t stream);
 
+/* ---- I3D feature tower of the FVD evaluation, forward only (csrc/i3d.hip; fvd/pytorch_i3d.py InceptionI3d,
+ *      fvd/fvd.py:7-50, run after every epoch by eval/eval.py:128-280).  Activations are channels-last
+ *      [N][T][H][W][C]; weights [Co][kt][kh][kw][Ci] with eval-mode BatchNorm folded in by the host.  The
+ *      1x1x1 units are plain products on uva_gemm (bias + UVA_ACT_RELU, ldc = the concat's channel count).
+ * uva_conv3d: out[m (n,ot,oh,ow)][coff + co] = act(bias[co] + sum_{kt,kh,kw,ci} in[n, ot st + kt - pt,
+ *      oh sh + kh - ph, ow sw + kw - pw, ci] w[co][kt][kh][kw][ci]), zero outside the input (Unit3D.forward's
+ *      F.pad + Conv3d(padding 0) + folded bn + relu, pytorch_i3d.py:82-107; the caller passes the FRONT pads, the
+ *      back pads follow from To / Ho / Wo).  act: UVA_ACT_NONE or UVA_ACT_RELU.  Output rows have stride ldc
+ *      channels and start at channel coff, so an Inception module's branches write their slices of the
+ *      concatenated tensor (pytorch_i3d.py:159-164, no torch.cat pass).  dtype bf16: in / w / out bf16,
+ *      implicit GEMM on v_mfma_f32_16x16x32_bf16, fp32 accumulation, no column matrix, Ci % 8 == 0; dtype fp32:
+ *      the VALU parity route, Ci % 4 == 0.  Both: Co, ldc, coff % 4 == 0, in / w 16-B aligned, out 16-B (fp32) or
+ *      8-B (bf16) aligned, ldc >= coff + Co, every window starting inside the front-padded input.  The stem
+ *      (7x7x7 / stride 2 on RGB) runs on its input padded to 8 channels (uva_fvd_preprocess writes that) with
+ *      zero weights on channels 3 .. 7.  Anything else: hipErrorInvalidValue, nothing launched.
+ * uva_conv3d_route: uva_conv3d's own selection code up to the launch, no device work: 0 = conv3d_f32 (VALU),
+ *      1 = conv3d_mfma, 3x3x3 / stride-1 form (compile-time taps), 2 = conv3d_mfma, general kernel / stride (the
+ *      stem), < 0 = -hipError. */
+int uva_conv3d(int dtype, const void* in, const void* w, void* out, const float* bias, int N, int T, int H, int W, int Ci,
+               int Co, int KT, int KH, int KW, int st, int sh, int sw, int pt, int ph, int pw, int To, int Ho, int Wo,
+               long long ldc, int coff, int act, hipStream_t stream);
+int uva_conv3d_route(int dtype, const void* in, const void* w, void* out, const float* bias, int N, int T, int H, int W,
+                     int Ci, int Co, int KT, int KH, int KW, int st, int sh, int sw, int pt, int ph, int pw, int To,
+                     int Ho, int Wo, long long ldc, int coff, int act);
+/* uva_maxpool3d: MaxPool3dSamePadding (pytorch_i3d.py:8-35: F.pad with zeros, then MaxPool3d(padding 0)): a
+ *      window position outside the input contributes the value 0 to the maximum, not -inf.  Contiguous in /
+ *      out, fp32 or bf16, C % 4 == 0, 16-B (fp32) / 8-B (bf16) aligned; front pads as uva_conv3d. */
+int uva_maxpool3d(int dtype, const void* in, void* out, int N, int T, int H, int W, int C, int KT, int KH, int KW, int st,
+                  int sh, int sw, int pt, int ph, int pw, int To, int Ho, int Wo, hipStream_t stream);
+/* uva_i3d_head: out [N][num_classes] fp32 = mean over the T - 1 time positions of (bias + w . AvgPool3d([2, 7, 7],
+ *      stride 1)(x)) for x [N][T][7][7][C] (fp32 or bf16), w fp32 [num_classes][C] (pytorch_i3d.py:408-413; the
+ *      dropout is in eval()).  The pooled rows (sum / 98, fp32) go through uva_gemm in fp32 on both routes; the
+ *      time mean is sum / (T - 1).  workspace: uva_i3d_head_workspace floats.  H, W other than 7 x 7 or T < 2:
+ *      hipErrorInvalidValue. */
+long long uva_i3d_head_workspace(int N, int T, int C, int num_classes);
+int uva_i3d_head(int dtype, const void* x, const float* w, const float* bias, float* out, int N, int T, int H, int W, int C,
+                 int num_classes, float* workspace, long long ws_floats, hipStream_t stream);
+/* uva_fvd_preprocess (fvd.py:7-44): videos uint8 [B][T][Hin][Win][3] -> out [B][T][S][S][Cpad] (odt fp32 / bf16):
+ *      x / 255, bilinear resize (align_corners = False, no antialias) of the shorter side to S with ceil on the
+ *      other, centre crop S x S, (v - 0.5) * 2; channels 3 .. Cpad - 1 are written as zeros (Cpad = 8 for the
+ *      stem).  The source coordinate is kept as an exact integer fraction: the cell index is exact and each
+ *      interpolation weight is one correctly rounded fp32 division. */
+int uva_fvd_preprocess(const void* videos, int odt, void* out, int B, int T, int Hin, int Win, int S, int Cpad,
+                       hipStream_t stream);
+
 /* ---- KL-VAE encoder plumbing (vae/vaekl.py, utils/data_utils.py) ---------------------
  * uva_resize_select: obs image [B,T,3,Hin,Win] fp32 in [0,1] -> NHWC [B*nsel,256,256,Cpad]
  *   frames sel[] (select_frames, data_utils.py:140-158), bilinear align_corners=False

@@ -833,3 +833,81 @@ def clip_pool(ids, x, out, index=None):
     if index is not None and not (index.dtype == torch.int32 and index.numel() == B and index.is_contiguous()):
         raise ValueError("clip_pool: index must be contiguous int32 [B]")
     _call("uva_clip_pool", ptr(ids), _int_code(ids, "clip_pool ids"), ptr(x), ptr(out), ptr(index), B, L, D, stream())
+
+
+# ---- I3D feature tower (csrc/i3d.hip; forward only) ------------------------------------------------------
+CONV3D_FORMS = ("f32_valu", "mfma_333", "mfma_general")
+
+
+def same_pad_3d(size, kernel, stride):
+    """Unit3D / MaxPool3dSamePadding's TF 'same' padding: per axis (front pad, output extent); the back pad
+    (total - front) is implied by the output extent"""
+    out = []
+    for s, k, st in zip(size, kernel, stride):
+        total = max(k - st, 0) if s % st == 0 else max(k - s % st, 0)
+        out.append((total // 2, (s + total - k) // st + 1))
+    return out
+
+
+def _conv3d_args(x, w, out, bias, stride, pads, out_size, coff, act):
+    N, T, H, W, Ci = x.shape
+    Co, KT, KH, KW, Ci2 = w.shape
+    To, Ho, Wo = out_size
+    if not (x.is_contiguous() and w.is_contiguous()) or Ci2 != Ci or x.dtype != w.dtype or x.dtype != out.dtype:
+        raise ValueError(f"conv3d: x {tuple(x.shape)} {x.dtype}, w {tuple(w.shape)} {w.dtype}, out {out.dtype}")
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != N * To * Ho * Wo or out.shape[1] < coff + Co:
+        raise ValueError(f"conv3d: out {tuple(out.shape)} for {N * To * Ho * Wo} rows, channels {coff}..{coff + Co}")
+    if bias is not None and not (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == Co):
+        raise ValueError("conv3d: fp32 bias [Co] expected")
+    return (dt(x), ptr(x), ptr(w), ptr(out), ptr(bias), N, T, H, W, Ci, Co, KT, KH, KW, *stride, *pads, To, Ho, Wo,
+            out.stride(0), coff, ACT[act])
+
+
+def conv3d(x, w, out, bias=None, stride=(1, 1, 1), pads=(0, 0, 0), out_size=None, coff=0, act="none"):
+    """out [N To Ho Wo, ldc] channels coff .. coff + Co = act(bias + conv3d(x [N,T,H,W,Ci], w [Co,kt,kh,kw,Ci]))
+    with the front pads `pads` (zero outside); bf16 -> MFMA implicit GEMM, fp32 -> VALU (uva_conv3d)"""
+    args = _conv3d_args(x, w, out, bias, stride, pads, out_size, coff, act)
+    Co, KT, KH, KW, Ci = w.shape
+    with _traced(f"conv3d {'bf16' if dt(x) else 'f32'} {KT}x{KH}x{KW} Ci{Ci} Co{Co} M{out.shape[0]}",
+                 2.0 * out.shape[0] * Co * KT * KH * KW * Ci):
+        _call("uva_conv3d", *args, stream())
+
+
+def conv3d_route(x, w, out, bias=None, stride=(1, 1, 1), pads=(0, 0, 0), out_size=None, coff=0, act="none"):
+    """the form conv3d() takes for exactly these arguments (a CONV3D_FORMS name); launches nothing"""
+    code = lib().query("uva_conv3d_route", *_conv3d_args(x, w, out, bias, stride, pads, out_size, coff, act))
+    if code < 0:
+        raise RuntimeError(f"uva_conv3d_route failed with hipError {-code}")
+    return CONV3D_FORMS[code]
+
+
+def maxpool3d(x, out, kernel, stride, pads, out_size):
+    """out [N,To,Ho,Wo,C] = max pool of x [N,T,H,W,C] whose padding contributes 0 (uva_maxpool3d)"""
+    N, T, H, W, C = x.shape
+    To, Ho, Wo = out_size
+    if not (x.is_contiguous() and out.is_contiguous() and x.dtype == out.dtype) or \
+            tuple(out.shape) != (N, To, Ho, Wo, C):
+        raise ValueError(f"maxpool3d: x {tuple(x.shape)} {x.dtype}, out {tuple(out.shape)} {out.dtype}")
+    _call("uva_maxpool3d", dt(x), ptr(x), ptr(out), N, T, H, W, C, *kernel, *stride, *pads, To, Ho, Wo, stream())
+
+
+def i3d_head(x, w, bias, out):
+    """out [N, classes] fp32 = time mean of (bias + w . avgpool[2,7,7](x)), x [N,T,7,7,C] (uva_i3d_head)"""
+    N, T, H, W, C = x.shape
+    K = w.shape[0]
+    if not (x.is_contiguous() and w.is_contiguous() and out.is_contiguous() and w.dtype == torch.float32 and
+            out.dtype == torch.float32 and tuple(w.shape) == (K, C) and tuple(out.shape) == (N, K) and
+            bias.dtype == torch.float32 and bias.numel() == K):
+        raise ValueError(f"i3d_head: x {tuple(x.shape)}, w {tuple(w.shape)}, out {tuple(out.shape)}")
+    n = lib().query("uva_i3d_head_workspace", N, T, C, K)
+    ws = torch.empty(max(int(n), 1), dtype=torch.float32, device=x.device)
+    _call("uva_i3d_head", dt(x), ptr(x), ptr(w), ptr(bias), ptr(out), N, T, H, W, C, K, ptr(ws), ws.numel(), stream())
+
+
+def fvd_preprocess(videos, out, size=224):
+    """out [B,T,size,size,Cpad] (fp32 / bf16) from uint8 videos [B,T,H,W,3] (uva_fvd_preprocess)"""
+    B, T, H, W, C = videos.shape
+    if videos.dtype != torch.uint8 or C != 3 or not videos.is_contiguous() or not out.is_contiguous() or \
+            tuple(out.shape[:4]) != (B, T, size, size) or videos.device != out.device:
+        raise ValueError(f"fvd_preprocess: videos {tuple(videos.shape)} {videos.dtype}, out {tuple(out.shape)}")
+    _call("uva_fvd_preprocess", ptr(videos), dt(out), ptr(out), B, T, H, W, size, out.shape[4], stream())

@@ -25,8 +25,13 @@ MI355X differences (results unchanged):
     does not call resize_image.
   * step logs are read back one step late (a pinned host copy + event instead of three
     blocking .item() calls), so the host keeps queueing the next step.
-  * epoch-end FVD / action-L2 evaluation and env rollouts are out of scope; the
-    checkpoint's top-k monitor falls back to train_loss when the configured key is absent.
+  * the epoch-end evaluation (workspace:342-376 -> eval/eval.py) runs on rank 0, on the EMA policy when
+    training.use_ema, in the reference's order and under its conditions, but only when asked for: FVD
+    (predict_video) when training.i3d_pretrained_path names a local I3D weight file (nothing is
+    downloaded; training.fvd_precision fp32 | bf16, default fp32), action L2 (predict_action, no
+    env_runner) when training.eval_action_l2 is true.  Their keys (video_fvd,
+    val_action_l2_distances) reach the top-k manager; env rollouts stay out of scope, and
+    the top-k monitor still falls back to train_loss while its configured key is absent.
 """
 import copy
 import json
@@ -85,11 +90,12 @@ class TopKCheckpointManager:
         if self.monitor_key in data:
             key, mode, fmt = self.monitor_key, self.mode, self.format_str
         else:
-            # Difference from the reference (which raises KeyError): its monitor keys (test_mean_score,
-            # val_action_l2_distances) come from env-runner / validation paths this workspace does not
-            # run, so a call without the configured key ranks by train_loss (min) under a file name
-            # that says so -- per call, in a ranking of its own: the configured key, once logged,
-            # is used again
+            # Difference from the reference (which raises KeyError): test_mean_score comes from env-runner
+            # rollouts this workspace does not run, and video_fvd / val_action_l2_distances are logged only
+            # when the epoch-end evaluation is switched on (training.i3d_pretrained_path /
+            # training.eval_action_l2), so a call without the configured key ranks by train_loss (min)
+            # under a file name that says so -- per call, in a ranking of its own: the configured key,
+            # once logged, is used again
             if self.FALLBACK[0] not in data:
                 return None
             key, mode, fmt = self.FALLBACK
@@ -229,7 +235,53 @@ class TrainUnifiedVideoActionWorkspace(BaseWorkspace):
         self.model.train()
         # on-device training augmentation instead of the dataset workers' CPU one
         self.device_augment = bool(cfg.task.get("device_augment", False))
+        # epoch-end evaluation (workspace:342-376), rank 0 only, off unless asked for
+        self.val_dataloader, self.i3d = None, None
+        run_fvd, run_l2 = self.eval_plan()
+        if (run_fvd or run_l2) and self.rank == 0:
+            vkw = dict(cfg.val_dataloader)
+            if not torch.cuda.is_available():
+                vkw["pin_memory"] = False
+            self.val_dataloader = torch.utils.data.DataLoader(self.dataset.get_validation_dataset(), **vkw)
+            if run_fvd:
+                from ..fvd.i3d import load_i3d_pretrained
+                self.i3d = load_i3d_pretrained(cfg.training.i3d_pretrained_path, self.device,
+                                               precision=cfg.training.get("fvd_precision", "fp32") or "fp32")
         return self
+
+    # ---- epoch-end evaluation (workspace:342-376) ----------------------------------------------
+    def eval_plan(self):
+        """(run FVD, run action L2): the reference's conditions (predict_video; predict_action and no
+        env_runner) AND this build's opt-in keys -- with both keys absent nothing is evaluated and an
+        epoch logs what it always logged"""
+        cfg = self.cfg
+        pol = cfg.model.policy
+        run_fvd = bool(pol.autoregressive_model_params.get("predict_video", True)) and \
+            bool(cfg.training.get("i3d_pretrained_path"))
+        run_l2 = bool(pol.action_model_params.predict_action) and "env_runner" not in cfg.task and \
+            bool(cfg.training.get("eval_action_l2", False))
+        return run_fvd, run_l2
+
+    def evaluate_epoch(self, rng=None):
+        """-> the evaluation's log entries ({} when nothing is switched on or on a rank other than 0)"""
+        run_fvd, run_l2 = self.eval_plan()
+        if not (run_fvd or run_l2) or self.rank != 0:
+            return {}
+        from ..eval import eval as E
+        cfg = self.cfg
+        policy = self.ema_model if cfg.training.use_ema else self.model
+        policy.eval()
+        log = {}
+        try:
+            if run_fvd:
+                log.update(E.test_video_fvd(cfg, policy, self.val_dataloader, self.epoch, self.output_dir, self.device,
+                                            i3d=self.i3d, rng=rng))
+            if run_l2:
+                log.update(E.test_action_l2(cfg, policy, self.val_dataloader, self.epoch, self.output_dir,
+                                            self.device, rng=rng))
+        finally:
+            policy.train()
+        return log
 
     # ---- one training step (workspace:279-302) -------------------------------------------------
     def train_step(self, batch, rng=None):
@@ -285,6 +337,7 @@ class TrainUnifiedVideoActionWorkspace(BaseWorkspace):
                 losses.append(rec["train_loss"])
             step_log = {"train_loss": float(np.mean(losses)) if losses else float("nan"),
                         "global_step": self.global_step, "epoch": self.epoch}
+            step_log.update(self.evaluate_epoch())
             if self.epoch % cfg.training.checkpoint_every == 0 and self.rank == 0:
                 if cfg.checkpoint.save_last_ckpt:
                     self.save_checkpoint()
