@@ -340,6 +340,37 @@ int uva_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, void
 /* EMAModel.step over the flat buffer (ema_model.py:78-85): ema = d*ema + (1-d)*p (16-B aligned). */
 int uva_ema_update(float* ema, const float* p, long long n, float decay, hipStream_t stream);
 
+/* ---- gradient norm, clipping and the non-finite step guard (opt-in; csrc/optim.hip) ------ */
+/* uva_grad_sumsq: slot_sumsq[s] (device, n_slots <= 16 doubles) = sum of (double)g*(double)g over the
+ * ranges of slot s.  ranges: HOST table of n_ranges <= 64 triples (offset, length, slot) in elements of
+ * g[0, n_total); a range may start at any element.  Deterministic (fixed chunks of
+ * uva_grad_norm_chunk_elems() elements, fp64 partials in `work`, no atomics): a relaunch is bit-equal
+ * and the sum is non-finite exactly when an element is.  work: >= uva_grad_norm_workspace_bytes(n_total,
+ * n_ranges) bytes on the device (pure host query; -1 on invalid arguments).  More than 64 ranges or 16
+ * slots, a range outside the buffer or a slot outside [0, n_slots) -> hipErrorInvalidValue before any
+ * launch.  uva_grad_norm_chain_len(n_chunks): the longest chain of fp64 additions one element's square
+ * passes through in a slot of n_chunks chunks (the error bound of the sum is chain * 2^-53 relative). */
+long long uva_grad_norm_chunk_elems();
+long long uva_grad_norm_chain_len(long long n_chunks);
+long long uva_grad_norm_workspace_bytes(long long n_total, int n_ranges);
+int uva_grad_sumsq(const float* g, long long n_total, const long long* ranges, int n_ranges, int n_slots,
+                   double* slot_sumsq, void* work, long long work_bytes, hipStream_t stream);
+/* uva_grad_guard: rec[4 + n_slots] (device floats) from the slot sums, computed in double:
+ *   rec[0] total_norm = sqrt(sum of the slots, in slot order) * grad_scale
+ *   rec[1] clip_coef  = min(1, max_norm / (total_norm + 1e-6)) (torch.nn.utils.clip_grad_norm_); 1 when
+ *          max_norm <= 0 (clipping off)
+ *   rec[2] skip       = 1 when skip_nonfinite and total_norm is not finite, else 0
+ *   rec[3] 0;  rec[4 + i] = sqrt(slot i) * grad_scale.
+ * With clipping on and skip_nonfinite off a non-finite norm gives torch's coefficient: 0 for Inf, NaN
+ * for NaN. */
+int uva_grad_guard(const double* slot_sumsq, int n_slots, float grad_scale, float max_norm, int skip_nonfinite,
+                   float* rec, hipStream_t stream);
+/* uva_adamw_ema with the gradient taken as g * grad_scale * rec[1]; when rec[2] != 0 it leaves p, m, v and
+ * the bf16 shadow untouched and still applies the EMA update against the unchanged p.  g is not rescaled. */
+int uva_adamw_ema_guarded(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16, long long n,
+                          long long n_decay, float lr, float b1, float b2, float eps, float wd, int step,
+                          float grad_scale, float ema_decay, const float* rec, hipStream_t stream);
+
 /* ---- fp8 (OCP e4m3) attention forward, head_dim 64 (BASELINE config 5 "fp8 MFMA attention";
  *      same call site as uva_attn_fwd: timm Attention / SDPA, mar_con_unified.py:201-249).
  * uva_attn_quant_fp8: per (batch, head, q|k|v, 64-row tile) power-of-two scales; rounds the bf16

@@ -40,7 +40,9 @@ class EMAModel:
         self.decay = 0.0
         self.optimization_step = 0
         self.flat = None          # fp32 EMA buffer in the live optimizer's flat layout
-        self._fused_step = None   # optimizer step count whose fused kernel applied our update
+        # the optimizer's step() call (opt.step_calls: a step its non-finite guard skipped still counts, its
+        # kernel applied the EMA all the same) whose fused kernel applied our update
+        self._fused_step = None
         self._opt_step_seen = None
         self._frozen = []         # (live param, ema param, live version at the last copy)
 
@@ -95,11 +97,11 @@ class EMAModel:
                 self._bind(new_model, opt)
                 fused = False
             else:
-                fused = self._fused_step is not None and self._fused_step == opt.step_count \
-                    and self._opt_step_seen != opt.step_count
+                fused = self._fused_step is not None and self._fused_step == opt.step_calls \
+                    and self._opt_step_seen != opt.step_calls
             if not fused:
                 ops.ema_update(self.flat, st.flat, self.decay)
-            self._opt_step_seen = opt.step_count
+            self._opt_step_seen = opt.step_calls
             self._fused_step = None
             frozen = []
             for p, q, ver in self._frozen:

@@ -512,6 +512,64 @@ def adamw_ema(p, g, m, v, ema, p_bf16, n_decay, lr, b1, b2, eps, wd, step, grad_
                float(ema_decay), stream())
 
 
+def adamw_ema_guarded(p, g, m, v, ema, p_bf16, n_decay, lr, b1, b2, eps, wd, step, grad_scale, ema_decay, rec):
+    """adamw_ema with the gradient scaled by rec[1] as well, and skipped (EMA still applied) when rec[2] != 0;
+    rec: the device record of grad_guard."""
+    if rec is None or rec.dtype != torch.float32 or rec.numel() < 4:
+        raise ValueError("adamw_ema_guarded: rec is grad_guard's fp32 device record")
+    _call("uva_adamw_ema_guarded", ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), ptr(p_bf16), p.numel(), int(n_decay),
+          float(lr), float(b1), float(b2), float(eps), float(wd), int(step), float(grad_scale),
+          float(ema_decay), ptr(rec), stream())
+
+
+GRAD_NORM_MAX_RANGES, GRAD_NORM_MAX_SLOTS = 64, 16
+
+
+def grad_norm_chunk_elems():
+    """elements per chunk of grad_sumsq (pure host)"""
+    return lib().query("uva_grad_norm_chunk_elems")
+
+
+def grad_norm_chain_len(n_elems, n_ranges=1):
+    """upper bound of the longest chain of fp64 additions one square passes through in a slot of
+    n_ranges ranges holding n_elems elements (pure host): the slot sum is within chain * 2^-53 relative"""
+    return lib().query("uva_grad_norm_chain_len", int(n_elems) // grad_norm_chunk_elems() + int(n_ranges))
+
+
+def grad_norm_workspace_bytes(n_total, n_ranges):
+    r = lib().query("uva_grad_norm_workspace_bytes", int(n_total), int(n_ranges))
+    if r < 0:
+        raise ValueError(f"grad_norm_workspace_bytes: refused n_total {n_total} n_ranges {n_ranges}")
+    return r
+
+
+def range_table(ranges):
+    """[(offset, length, slot)] -> the host table uva_grad_sumsq reads (keep it alive across the call)"""
+    flat = [int(x) for r in ranges for x in r]
+    return (ctypes.c_longlong * max(1, len(flat)))(*flat)
+
+
+def grad_sumsq(g, ranges, n_slots, slot_sumsq, work, table=None):
+    """slot_sumsq[s] (fp64, device) = sum of squares of g over the ranges [(offset, length, slot)] of slot s,
+    deterministic (uva_grad_sumsq); work: a device buffer of >= grad_norm_workspace_bytes bytes."""
+    if g.dtype != torch.float32 or not g.is_contiguous():
+        raise ValueError("grad_sumsq: one contiguous fp32 buffer")
+    if slot_sumsq.dtype != torch.float64 or slot_sumsq.numel() < n_slots:
+        raise ValueError("grad_sumsq: slot_sumsq holds n_slots doubles")
+    table = range_table(ranges) if table is None else table
+    _call("uva_grad_sumsq", ptr(g), g.numel(), ctypes.addressof(table), len(ranges), int(n_slots), ptr(slot_sumsq),
+          ptr(work), work.numel() * work.element_size(), stream())
+
+
+def grad_guard(slot_sumsq, n_slots, grad_scale, max_norm, skip_nonfinite, rec):
+    """rec[4 + n_slots] = total norm, clip coefficient, skip flag, 0, slot norms (uva_grad_guard);
+    max_norm None or <= 0: clipping off (coefficient 1)."""
+    if rec.dtype != torch.float32 or rec.numel() < 4 + n_slots:
+        raise ValueError("grad_guard: rec holds 4 + n_slots floats")
+    _call("uva_grad_guard", ptr(slot_sumsq), int(n_slots), float(grad_scale), float(max_norm or 0.0),
+          int(bool(skip_nonfinite)), ptr(rec), stream())
+
+
 def ema_update(ema, p, decay):
     """ema = decay * ema + (1 - decay) * p over two flat fp32 buffers (uva_ema_update)."""
     if ema.dtype != torch.float32 or p.dtype != torch.float32 or ema.numel() != p.numel():

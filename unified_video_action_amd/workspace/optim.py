@@ -148,9 +148,12 @@ _ADAMW_GROUP_KEYS = dict(amsgrad=False, foreach=None, maximize=False, capturable
 
 
 class FusedAdamWEMA(torch.optim.Optimizer):
-    """torch.optim.AdamW over flat buffers, one fused HIP pass per param group."""
+    """torch.optim.AdamW over flat buffers, one fused HIP pass per param group.  Optional (set_grad_guard):
+    the total / per-part gradient norm, clipping folded into that pass, and a guard that skips a step whose
+    gradient is not finite."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, named=None, prefix=""):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, named=None, prefix="",
+                 max_grad_norm=None, skip_nonfinite=False, grad_norm_parts=None):
         self._ready = False
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
         for g in self.param_groups:
@@ -162,11 +165,15 @@ class FusedAdamWEMA(torch.optim.Optimizer):
         self.store = ParamStore(groups, prefix)
         self.m = torch.zeros_like(self.store.flat)
         self.v = torch.zeros_like(self.store.flat)
-        self.step_count = 0
+        self._step_count = 0
+        self.step_calls = 0  # step() calls, skipped ones included: what the EMA hand-off keys on
         self.grad_scale = 1.0
         self.reducer = None
         self._ema_ref = None
+        self._guard = None
+        self._skipped = 0
         self._ready = True
+        self.set_grad_guard(max_grad_norm, skip_nonfinite, grad_norm_parts)
 
     # ---- torch.optim.Optimizer surface ----------------------------------------------------
     def add_param_group(self, param_group):
@@ -197,11 +204,20 @@ class FusedAdamWEMA(torch.optim.Optimizer):
         self._sync()
         if self.reducer is not None:
             self.reducer.finish()
-        self.step_count += 1
+        self._resolve()  # the previous step's skip decision, before this step's bias correction
+        self._step_count += 1
+        self.step_calls += 1
         ema = self.attached_ema()
         d = ema.get_decay(ema.optimization_step) if ema is not None else 0.0
         st = self.store
         red = self.reducer
+        rec = None
+        if self._guard is not None:
+            # the norm needs the fully reduced buffer: the deferred DP tail is waited for first (overlap_tail
+            # buys nothing here).  Every rank sees the same reduced buffer, hence the same decision
+            if red is not None:
+                red.wait_tail()
+            rec = self._launch_guard()
         late = red.tail_segments() if (red is not None and red.tail_handles) else []
         # a deferred DP tail (GradReducer.defer_tail): AdamW runs over everything else first, under
         # the tail's all-reduce, then over the tail once it has landed
@@ -212,19 +228,124 @@ class FusedAdamWEMA(torch.optim.Optimizer):
                 if n == 0:
                     continue
                 for o, k in _segments(off, n, late, phase):
-                    self._adamw(g, o, k, ema, d)
+                    self._adamw(g, o, k, ema, d, rec)
         if ema is not None:
-            ema.mark_fused(self.step_count)
+            ema.mark_fused(self.step_calls)
         RT.bump_params()
         return loss
 
-    def _adamw(self, g, o, k, ema, d):
+    def _adamw(self, g, o, k, ema, d, rec=None):
         st = self.store
         b1, b2 = g["betas"]
         sl = slice(o, o + k)
-        ops.adamw_ema(st.flat[sl], st.grad[sl], self.m[sl], self.v[sl], ema.flat[sl] if ema is not None else None,
-                      st.shadow[sl] if st.shadow is not None else None, k if g["weight_decay"] else 0,
-                      g["lr"], b1, b2, g["eps"], g["weight_decay"], self.step_count, self.grad_scale, d)
+        args = (st.flat[sl], st.grad[sl], self.m[sl], self.v[sl], ema.flat[sl] if ema is not None else None,
+                st.shadow[sl] if st.shadow is not None else None, k if g["weight_decay"] else 0,
+                g["lr"], b1, b2, g["eps"], g["weight_decay"], self._step_count, self.grad_scale, d)
+        if rec is None:
+            ops.adamw_ema(*args)
+        else:
+            ops.adamw_ema_guarded(*args, rec)
+
+    # ---- gradient norm, clipping, non-finite guard (off unless set) ---------------------------
+    @property
+    def step_count(self):
+        """applied steps (torch.optim.AdamW's per-parameter `step`): a step the guard skipped does not
+        count.  Reading it waits for the last step's record when the guard is on."""
+        self._resolve()
+        return self._step_count
+
+    @step_count.setter
+    def step_count(self, value):
+        self._resolve()
+        self._step_count = int(value)
+
+    def set_grad_guard(self, max_grad_norm=None, skip_nonfinite=False, grad_norm_parts=None):
+        """max_grad_norm: clip the total gradient norm (torch.nn.utils.clip_grad_norm_'s coefficient, folded
+        into the AdamW kernel's gradient scaling; the gradient buffer itself is NOT rescaled).
+        skip_nonfinite: a step whose gradient norm is NaN / Inf leaves the weights, both moments and the bf16
+        shadow untouched and does not advance the step count (the EMA still averages, as the reference's
+        ema.step runs every iteration).  grad_norm_parts: {name: module or parameters} whose norms are reported
+        beside the total; what they do not cover is the part "rest".  Any of the three switches the norm pass
+        on (grad_norm_parts = {} asks for the total alone); all unset switches it off again."""
+        self._resolve()
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if self.max_grad_norm is None and not self.skip_nonfinite and grad_norm_parts is None:
+            self._guard = None
+            return
+        names, table = grad_range_table(self.store, grad_norm_parts or {})
+        self._guard = dict(names=names, table=table, dev=None)
+
+    def _guard_buffers(self):
+        """device / pinned buffers of the guard, (re)made on the store's current device"""
+        gd, st = self._guard, self.store
+        if gd["dev"] != st.device:
+            n_slots = len(gd["names"])
+            # (a module move re-binds the parameters at the same offsets: the table stays valid)
+            gd["ctable"] = ops.range_table(gd["table"])
+            gd["work"] = torch.empty(ops.grad_norm_workspace_bytes(st.total, len(gd["table"])) // 8,
+                                     dtype=torch.float64, device=st.device)
+            gd["sums"] = torch.zeros(n_slots, dtype=torch.float64, device=st.device)
+            gd["rec"] = torch.zeros(4 + n_slots, dtype=torch.float32, device=st.device)
+            gd["host"] = torch.zeros(4 + n_slots, dtype=torch.float32, pin_memory=st.device.type == "cuda")
+            gd["event"], gd["pending"], gd["last"] = None, False, None
+            gd["dev"] = st.device
+        return gd
+
+    def _launch_guard(self):
+        """norm pass + guard record on the current stream, the record copied to pinned memory behind an
+        event (read at the start of the next step: no host synchronisation here) -> the device record"""
+        gd = self._guard_buffers()
+        n_slots = len(gd["names"])
+        ops.grad_sumsq(self.store.grad, gd["table"], n_slots, gd["sums"], gd["work"], table=gd["ctable"])
+        ops.grad_guard(gd["sums"], n_slots, self.grad_scale, self.max_grad_norm, self.skip_nonfinite, gd["rec"])
+        gd["host"].copy_(gd["rec"], non_blocking=True)
+        if gd["event"] is None:
+            gd["event"] = torch.cuda.Event()
+        gd["event"].record()
+        gd["pending"] = True
+        return gd["rec"]
+
+    def _resolve(self):
+        """take the last guarded step's decision from its pinned record: a skipped step gives its count
+        back, so the next applied step's bias correction is torch.optim.AdamW's that never saw it"""
+        gd = self._guard
+        if gd is None or not gd.get("pending"):
+            return
+        gd["event"].synchronize()
+        gd["pending"] = False
+        gd["last"] = gd["host"].tolist()
+        if gd["last"][2] != 0.0:
+            self._step_count -= 1
+            self._skipped += 1
+
+    @property
+    def grad_record(self):
+        """the device record of the last step (fp32: total norm, clip coefficient, skipped, 0, then the part
+        norms in grad_part_names order), or None with the guard off; reading it does not block"""
+        return self._guard.get("rec") if self._guard is not None and self._guard["dev"] is not None else None
+
+    @property
+    def grad_part_names(self):
+        return list(self._guard["names"]) if self._guard is not None else []
+
+    def grad_stats(self):
+        """{grad_norm, grad_clip_coef, skipped, grad_norm/<part>...} of the last completed step (waits for its
+        record); {} before the first guarded step"""
+        self._resolve()
+        gd = self._guard
+        if gd is None or gd.get("last") is None:
+            return {}
+        return grad_stats_dict(gd["last"], gd["names"])
+
+    @property
+    def skipped_steps(self):
+        """steps the non-finite guard skipped in this process (not part of state_dict(): the torch AdamW
+        layout stays as it is, and the count restarts with the process)"""
+        self._resolve()
+        return self._skipped
 
     @property
     def overlap_tail(self):
@@ -264,13 +385,14 @@ class FusedAdamWEMA(torch.optim.Optimizer):
     # ---- torch.optim.AdamW state_dict layout -------------------------------------------------
     def state_dict(self):
         st = self.store
+        step_count = self.step_count
         state, groups, idx = {}, [], 0
         for g, names in zip(self.param_groups, st.groups):
             ids = []
             for n, p in names:
-                if self.step_count > 0:
+                if step_count > 0:
                     o, k = st.offsets[id(p)]
-                    state[idx] = {"step": torch.tensor(float(self.step_count)),
+                    state[idx] = {"step": torch.tensor(float(step_count)),
                                   "exp_avg": self.m[o:o + k].view_as(p), "exp_avg_sq": self.v[o:o + k].view_as(p)}
                 ids.append(idx)
                 idx += 1
@@ -308,6 +430,52 @@ class FusedAdamWEMA(torch.optim.Optimizer):
             for k in ("lr", "betas", "eps", "weight_decay", "initial_lr"):
                 if k in theirs:
                     mine[k] = tuple(theirs[k]) if k == "betas" else theirs[k]
+
+
+def grad_stats_dict(rec, names):
+    """a guard record (list of floats) -> the log entries"""
+    out = {"grad_norm": rec[0], "grad_clip_coef": rec[1], "skipped": int(rec[2] != 0.0)}
+    for i, n in enumerate(names):
+        out[f"grad_norm/{n}"] = rec[4 + i]
+    return out
+
+
+def grad_range_table(store, parts):
+    """-> (slot names, [(offset, length, slot)]): the ranges of every named part (a module, or an iterable of
+    parameters; ParamStore.ranges_of), then slot "rest" for what they leave of the group ranges.  The table
+    covers every element of every group range exactly once; the padding between groups is in no range."""
+    names = list(parts) + ["rest"]
+    if "rest" in parts:
+        raise ValueError('grad_norm_parts: "rest" names what the parts do not cover')
+    table = []
+    for slot, name in enumerate(parts):
+        obj = parts[name]
+        objs = obj if isinstance(obj, (list, tuple)) else [obj]
+        params = [p for o in objs if o is not None
+                  for p in ([o] if isinstance(o, torch.Tensor) else o.parameters() if hasattr(o, "parameters") else o)]
+        table += [(o, k, slot) for o, k in store.ranges_of(params) if k > 0]
+    table.sort()
+    pos_ok = 0
+    for o, k, _ in table:
+        if o < pos_ok:
+            raise ValueError("grad_norm_parts: two parts share a parameter")
+        pos_ok = o + k
+    rest, slot = [], len(names) - 1
+    for start, n in store.group_ranges:
+        pos = start
+        for o, k, _ in table:
+            if o + k <= start or o >= start + n:
+                continue
+            if o > pos:
+                rest.append((pos, o - pos, slot))
+            pos = o + k
+        if pos < start + n:
+            rest.append((pos, start + n - pos, slot))
+    table = sorted(table + rest)
+    if len(names) > ops.GRAD_NORM_MAX_SLOTS or len(table) > ops.GRAD_NORM_MAX_RANGES:
+        raise ValueError(f"grad_norm_parts: {len(names)} parts in {len(table)} ranges; the norm kernel takes "
+                         f"{ops.GRAD_NORM_MAX_SLOTS} parts in {ops.GRAD_NORM_MAX_RANGES} ranges")
+    return names, table
 
 
 def _segments(off, n, late, phase):

@@ -124,20 +124,26 @@ class TopKCheckpointManager:
 
 
 class _LaggedLog:
-    """step losses copied to pinned host memory behind an event; read one step later."""
+    """step values copied to pinned host memory behind an event; read one step later."""
+
+    NAMES = ("train_loss", "diffusion_loss", "action_loss")
 
     def __init__(self):
         self.pending = None
 
-    def push(self, tensors, meta):
-        host = torch.empty(len(tensors), dtype=torch.float32, pin_memory=torch.cuda.is_available())
+    def push(self, tensors, meta, names=NAMES, record=None, decode=None):
+        """tensors: one scalar device tensor per name.  record: an optional fp32 device vector that rides the
+        same copy (the optimizer's gradient record); decode(list of its floats) -> further log entries."""
         dev = torch.stack([t.detach().float().reshape(()) for t in tensors])
+        if record is not None:
+            dev = torch.cat([dev, record.detach().float().reshape(-1)])
+        host = torch.empty(dev.numel(), dtype=torch.float32, pin_memory=torch.cuda.is_available())
         host.copy_(dev, non_blocking=True)
         ev = None
         if dev.is_cuda:
             ev = torch.cuda.Event()
             ev.record()
-        prev, self.pending = self.pending, (host, ev, meta)
+        prev, self.pending = self.pending, (host, ev, meta, tuple(names), decode)
         return self._read(prev)
 
     def flush(self):
@@ -148,12 +154,14 @@ class _LaggedLog:
     def _read(item):
         if item is None:
             return None
-        host, ev, meta = item
+        host, ev, meta, names, decode = item
         if ev is not None:
             ev.synchronize()
         vals = host.tolist()
         out = dict(meta)
-        out.update(train_loss=vals[0], diffusion_loss=vals[1], action_loss=vals[2])
+        out.update(zip(names, vals))
+        if decode is not None:
+            out.update(decode(vals[len(names):]))
         return out
 
 
@@ -181,8 +189,41 @@ class TrainUnifiedVideoActionWorkspace(BaseWorkspace):
         # the encoder-input gradients while their deferred all-reduce is still in flight
         if hasattr(self.optimizer, "overlap_tail"):
             self.optimizer.overlap_tail = int(cfg.training.get("gradient_accumulate_every", 1) or 1) == 1
+        self._configure_grad_guard()
         self.global_step = 0
         self.epoch = 0
+
+    # ---- gradient norm / clipping / non-finite guard (opt-in keys; off when all are absent) ---
+    def grad_guard_on(self):
+        t = self.cfg.training
+        return t.get("max_grad_norm") is not None or bool(t.get("skip_nonfinite_steps", False)) or \
+            bool(t.get("log_grad_norm", False))
+
+    def _configure_grad_guard(self):
+        """training.max_grad_norm / skip_nonfinite_steps / log_grad_norm -> the optimizer's guard, with the
+        norm reported for the encoder, the decoder, the video heads, the action heads and the rest.
+        (get_optimizer keeps the reference's signature, so the options are set after it.)"""
+        self._skipped_logged = 0
+        if not self.grad_guard_on():
+            return
+        if not hasattr(self.optimizer, "set_grad_guard"):
+            raise RuntimeError("training.max_grad_norm / skip_nonfinite_steps / log_grad_norm need the flat-buffer "
+                               "optimizer (FusedAdamWEMA)")
+        t, m = self.cfg.training, self.model.model
+        parts = {"encoder": [getattr(m, "encoder_blocks", None)], "decoder": [getattr(m, "decoder_blocks", None)],
+                 "video_head": [getattr(m, "diffloss", None), getattr(m, "diffloss_wrist", None)],
+                 "action_head": [getattr(m, "diffactloss", None), getattr(m, "diffproploss", None)]}
+        mg = t.get("max_grad_norm")
+        self.optimizer.set_grad_guard(max_grad_norm=None if mg is None else float(mg),
+                                      skip_nonfinite=bool(t.get("skip_nonfinite_steps", False)), grad_norm_parts=parts)
+
+    def _grad_log(self, vals):
+        """the lagged gradient record -> log entries; skipped_steps counts the records seen so far"""
+        from .optim import grad_stats_dict
+        out = grad_stats_dict(vals, self.optimizer.grad_part_names)
+        self._skipped_logged += out.pop("skipped")
+        out["skipped_steps"] = self._skipped_logged
+        return out
 
     # ---- setup (the part of run() before the loop) ------------------------------------------
     def setup(self, device=None):
@@ -325,7 +366,9 @@ class TrainUnifiedVideoActionWorkspace(BaseWorkspace):
                 raw, lv, la = self.train_step(batch)
                 meta = {"global_step": self.global_step, "epoch": self.epoch,
                         "lr": self.lr_scheduler.get_last_lr()[0]}
-                rec = emit(lag.push([raw, lv if lv is not None else zero, la if la is not None else zero], meta))
+                grec = self.optimizer.grad_record if self.grad_guard_on() else None
+                rec = emit(lag.push([raw, lv if lv is not None else zero, la if la is not None else zero], meta,
+                                    record=grec, decode=self._grad_log if grec is not None else None))
                 if rec is not None:
                     losses.append(rec["train_loss"])
                 if batch_idx != n_batches - 1:
