@@ -282,6 +282,20 @@ int uva_p_sample_step(int odt, const void* out, long long ld_out, const float* x
                       const float* coef, float* x_new, int xdt, void* x_net, int clip, int rows, int C,
                       hipStream_t stream);
 
+/* ---- DDIM sampler step (gaussian_diffusion.py:543-590 ddim_sample, eps model) ------------------
+ * The operand contract of uva_p_sample_step; only the first C columns of `out` (eps) are read.
+ * coef: HOST array of 6 floats {sqrt_recip_ac, sqrt_recipm1_ac, a = sqrt(ac_prev),
+ * b = sqrt(max(0, 1 - ac_prev - sigma^2)), s = sigma * (t != 0), temperature} with
+ * sigma = eta sqrt((1 - ac_prev) / (1 - ac)) sqrt(1 - ac / ac_prev):
+ *   x0 = k0 x - k1 eps_model [clamped to +-1 when clip];  eps = (k0 x - x0) / k1;
+ *   x_new = a x0 + b eps + s noise temperature.
+ * s == 0: noise is not read and may be null (s != 0 with a null noise is refused).  The temperature
+ * scales the noise term only (an extension; the reference's ddim_sample has none): no effect at eta = 0.
+ * Refused (hipErrorInvalidValue, nothing launched): rows <= 0, C <= 0, ld_out < 2C. */
+int uva_ddim_step(int odt, const void* out, long long ld_out, const float* x, const float* noise,
+                  const float* coef, float* x_new, int xdt, void* x_net, int clip, int rows, int C,
+                  hipStream_t stream);
+
 /* ---- few-row fused linear of the action sampler (inference, bf16; diffusion_loss.py:142-189)
  * out[R,N] = epi(A' W^T + bias), W bf16 [N,K] (K in {256, 512, 1024}), R any.
  * ln = 1: A = fp32 residual rows x [R, lda]; A' = (LN(x)[*lnw + lnb]) * (1 + scale) + shift

@@ -198,6 +198,37 @@ __global__ void p_sample_step_kernel(const void* __restrict__ out, int odt, long
   }
 }
 
+// One step of GaussianDiffusion.ddim_sample (gaussian_diffusion.py:543-590) for the eps model:
+//   x0    = sqrt_recip_ac*x - sqrt_recipm1_ac*eps_model   [clamped to [-1, 1] when clip_denoised]
+//   eps   = (sqrt_recip_ac*x - x0) / sqrt_recipm1_ac      (re-derived: differs from eps_model where x0 clipped)
+//   x_new = a*x0 + b*eps + s*noise*temperature
+// a = sqrt(ac_prev), b = sqrt(max(0, 1 - ac_prev - sigma^2)), s = sigma*[t != 0], formed on the host in
+// float64 and cast once.  Only the eps half of `out` is read.  s == 0 (eta = 0, or the t = 0 step): noise is
+// not read and may be null.  The temperature scales the noise term only (p_sample_step_kernel's convention;
+// the reference's ddim_sample has none), so it has no effect at eta = 0.
+struct DdimCoef {
+  float sqrt_recip_ac, sqrt_recipm1_ac, a, b, s, temperature;
+};
+
+__global__ void ddim_step_kernel(const void* __restrict__ out, int odt, long long ld_out, const float* x,
+                                 const float* __restrict__ noise, DdimCoef k, float* x_new, void* x_net, int xdt,
+                                 int clip, int rows, int C) {
+  long long n = (long long)rows * C;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    long long r = i / C;
+    int c = (int)(i % C);
+    float em = ldx2(out, odt, r * ld_out + c);
+    float kx = k.sqrt_recip_ac * x[i];
+    float x0 = kx - k.sqrt_recipm1_ac * em;
+    if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    float eps = (kx - x0) / k.sqrt_recipm1_ac;
+    float xn = k.a * x0 + k.b * eps;
+    if (k.s != 0.0f) xn += k.s * noise[i] * k.temperature;
+    x_new[i] = xn;
+    if (x_net) stx2(x_net, xdt, i, xn);
+  }
+}
+
 static inline dim3 grid_for(long long n) {
   long long b = (n + 255) / 256;
   if (b > 8192) b = 8192;
@@ -248,6 +279,18 @@ extern "C" int uva_p_sample_step(int odt, const void* out, long long ld_out, con
   PStepCoef k{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7]};
   p_sample_step_kernel<<<grid_for((long long)rows * C), 256, 0, s>>>(out, odt, ld_out, x, noise, k, x_new, x_net,
                                                                       xdt, clip, rows, C);
+  UVA_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int uva_ddim_step(int odt, const void* out, long long ld_out, const float* x, const float* noise,
+                             const float* coef, float* x_new, int xdt, void* x_net, int clip, int rows, int C,
+                             hipStream_t s) {
+  if (rows <= 0 || C <= 0 || ld_out < 2 * C) return (int)hipErrorInvalidValue;
+  DdimCoef k{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
+  if (k.s != 0.0f && !noise) return (int)hipErrorInvalidValue;
+  ddim_step_kernel<<<grid_for((long long)rows * C), 256, 0, s>>>(out, odt, ld_out, x, noise, k, x_new, x_net, xdt,
+                                                                  clip, rows, C);
   UVA_LAUNCH_CHECK();
   return 0;
 }

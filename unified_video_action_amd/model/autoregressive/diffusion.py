@@ -56,6 +56,8 @@ def cosine_tables(T=1000, respacing=""):
     return {
         "timestep_map": np.asarray(keep, np.int64),
         "betas": betas,
+        "ac": ac,
+        "ac_prev": ac_prev,
         "sqrt_ac": np.sqrt(ac),
         "sqrt_1mac": np.sqrt(1.0 - ac),
         "coef1": betas * np.sqrt(ac_prev) / (1.0 - ac),
@@ -97,3 +99,26 @@ class SamplingSchedule:
         self.steps = []  # (spaced t, base timestep, coef[8] without temperature)
         for t in reversed(range(self.S)):
             self.steps.append((t, int(tb["timestep_map"][t]), [c[t] for c in cols] + [1.0 if t != 0 else 0.0]))
+        self._ddim = {}
+
+    def ddim_steps(self, eta=0.0):
+        """DDIM rows of the same spaced process (gaussian_diffusion.py:543-590 ddim_sample), in loop order:
+        (spaced t, base timestep, [sqrt_recip_ac, sqrt_recipm1_ac, a, b, s]) with a = sqrt(ac_prev),
+        b = sqrt(1 - ac_prev - sigma^2), s = sigma [t != 0] and
+        sigma = eta sqrt((1 - ac_prev) / (1 - ac)) sqrt(1 - ac / ac_prev), all in float64 and cast once to fp32
+        (the reference forms them in fp32 from fp32 table entries).  At t = 0 ac_prev is 1, so sigma and the
+        radicand are exactly 0; the max(0, .) only guards the cast."""
+        eta = float(eta)
+        if not 0.0 <= eta <= 1.0:  # beyond 1 the radicand 1 - ac_prev - sigma^2 goes negative
+            raise ValueError(f"ddim eta must be in [0, 1], got {eta}")
+        if eta not in self._ddim:
+            tb = self.np
+            ac, ac_prev = tb["ac"], tb["ac_prev"]
+            sigma = eta * np.sqrt((1.0 - ac_prev) / (1.0 - ac)) * np.sqrt(1.0 - ac / ac_prev)
+            b = np.sqrt(np.maximum(0.0, 1.0 - ac_prev - sigma * sigma))
+            s = np.where(np.arange(self.S) != 0, sigma, 0.0)
+            f32 = lambda a: [float(v) for v in np.asarray(a, np.float64).astype(np.float32)]
+            cols = [f32(tb["sqrt_recip_ac"]), f32(tb["sqrt_recipm1_ac"]), f32(np.sqrt(ac_prev)), f32(b), f32(s)]
+            self._ddim[eta] = [(t, int(tb["timestep_map"][t]), [c[t] for c in cols])
+                               for t in reversed(range(self.S))]
+        return self._ddim[eta]

@@ -116,8 +116,11 @@ def _cols_k7(x):
 class DiffActLoss(nn.Module):
     def __init__(self, target_channels, z_channels, depth, width, num_sampling_steps, grad_checkpointing=False,
                  n_frames=4, act_diff_training_steps=1000, act_diff_testing_steps="100", act_model_type="conv_fc",
-                 **kwargs):
+                 act_sampler="ddpm", act_ddim_eta=0.0, **kwargs):
         super().__init__()
+        if act_sampler not in ActionSampler.METHODS:
+            raise ValueError(f"unknown act_sampler {act_sampler!r}: expected one of {ActionSampler.METHODS}")
+        self.act_sampler, self.act_ddim_eta = act_sampler, float(act_ddim_eta)
         self.in_channels = target_channels
         self.n_frames = n_frames
         self.act_model_type = act_model_type
@@ -185,13 +188,18 @@ class DiffActLoss(nn.Module):
         bsz, seq_len, _ = c.shape
         rows = bsz * seq_len
         if self._sampler is None:
-            self._sampler = ActionSampler(self.net, self.act_diff_testing_steps)
+            self._sampler = ActionSampler(self.net, self.act_diff_testing_steps, method=self.act_sampler,
+                                          eta=self.act_ddim_eta)
         S = self._sampler.sched.S
         dev = z.device
         if noise is None:
             noise = torch.randn(rows, self.in_channels, device=dev)
-        if step_noise is None:
+        if not self._sampler.needs_step_noise:
+            step_noise = None  # DDIM at eta = 0: nothing is drawn, an injected tensor is ignored
+        elif step_noise is None:
             step_noise = torch.randn(S, rows, self.in_channels, device=dev)
+        if step_noise is not None:
+            step_noise = step_noise.to(dev, F32).reshape(S, rows, -1)
         x = self._sampler(c.reshape(rows, -1).float().contiguous(), noise.to(dev, F32).reshape(rows, -1),
-                          step_noise.to(dev, F32).reshape(S, rows, -1), temperature)
+                          step_noise, temperature)
         return x.reshape(bsz, seq_len, -1)

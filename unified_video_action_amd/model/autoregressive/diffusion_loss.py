@@ -157,8 +157,11 @@ class DiffLoss(nn.Module):
     """Diffusion Loss (diffusion_loss.py:8-66)."""
 
     def __init__(self, target_channels, z_channels, depth, width, num_sampling_steps, grad_checkpointing=False,
-                 **kwargs):
+                 video_sampler="ddpm", video_ddim_eta=0.0, **kwargs):
         super().__init__()
+        if video_sampler not in ("ddpm", "ddim"):
+            raise ValueError(f"unknown video_sampler {video_sampler!r}: expected 'ddpm' or 'ddim'")
+        self.video_sampler, self.video_ddim_eta = video_sampler, float(video_ddim_eta)
         self.in_channels = target_channels
         self.n_frames = kwargs.get("n_frames", 4)
         self.net = SimpleMLPAdaLN(target_channels, width, target_channels * 2, z_channels, depth, grad_checkpointing)
@@ -175,16 +178,20 @@ class DiffLoss(nn.Module):
             raise NotImplementedError("classifier-free guidance (forward_with_cfg) is not on the built path")
         from .sampler import ActionSampler
         if self._sampler is None:
-            self._sampler = ActionSampler(self.net, self.num_sampling_steps, clip_denoised=False)
+            self._sampler = ActionSampler(self.net, self.num_sampling_steps, clip_denoised=False,
+                                          method=self.video_sampler, eta=self.video_ddim_eta)
         R = z.shape[0]
         S = self._sampler.sched.S
         dev = z.device
         if noise is None:
             noise = torch.randn(R, self.in_channels, device=dev)
-        if step_noise is None:
+        if not self._sampler.needs_step_noise:
+            step_noise = None  # DDIM at eta = 0: nothing is drawn, an injected tensor is ignored
+        elif step_noise is None:
             step_noise = torch.randn(S, R, self.in_channels, device=dev)
-        return self._sampler(z.float().contiguous(), noise.to(dev, torch.float32),
-                             step_noise.to(dev, torch.float32), temperature)
+        if step_noise is not None:
+            step_noise = step_noise.to(dev, torch.float32)
+        return self._sampler(z.float().contiguous(), noise.to(dev, torch.float32), step_noise, temperature)
 
     def forward(self, target, z, mask=None, conf_score=None, text_latents=None, t=None, noise=None):
         bsz, seq_len, _ = target.shape

@@ -70,7 +70,8 @@ class MAR(nn.Module):
                  attn_dropout=0.1, proj_dropout=0.1, diffloss_d=3, diffloss_w=1024, diffloss_act_d=3,
                  diffloss_act_w=1024, num_sampling_steps="100", diffusion_batch_mul=4, grad_checkpointing=False,
                  predict_video=True, act_diff_training_steps=1000, act_diff_testing_steps="100",
-                 action_model_params={}, **kwargs):
+                 action_model_params={}, act_sampler="ddpm", act_ddim_eta=0.0, video_sampler="ddpm",
+                 video_ddim_eta=0.0, **kwargs):
         super().__init__()
         self.task_name = kwargs["task_name"]
         self.different_history_freq = kwargs.get("different_history_freq") or False
@@ -148,15 +149,19 @@ class MAR(nn.Module):
         self.predict_video = predict_video
         if predict_video:
             self.diffloss = DiffLoss(self.token_embed_dim, Dd, diffloss_d, diffloss_w, num_sampling_steps,
-                                     grad_checkpointing, n_frames=self.n_frames)
+                                     grad_checkpointing, n_frames=self.n_frames, video_sampler=video_sampler,
+                                     video_ddim_eta=video_ddim_eta)
             if self.predict_wrist_img:  # (:281-294)
                 self.diffloss_wrist = DiffLoss(self.token_embed_dim, Dd, diffloss_d, diffloss_w, num_sampling_steps,
-                                               grad_checkpointing, n_frames=self.n_frames)
+                                               grad_checkpointing, n_frames=self.n_frames,
+                                               video_sampler=video_sampler, video_ddim_eta=video_ddim_eta)
         if self.predict_action:
             self.diffactloss = DiffActLoss(act_dim, Dd, diffloss_act_d, diffloss_act_w, num_sampling_steps,
                                            grad_checkpointing, n_frames=self.n_frames,
                                            act_model_type=action_model_params.get("act_model_type", "conv_fc"),
-                                           act_diff_training_steps=act_diff_training_steps)
+                                           act_diff_training_steps=act_diff_training_steps,
+                                           act_diff_testing_steps=act_diff_testing_steps, act_sampler=act_sampler,
+                                           act_ddim_eta=act_ddim_eta)
         if self.predict_proprioception:
             # (:313-344) UMI: 6-d rotation targets; toolhang: eef pos + quat + gripper (9-d)
             if not (self.umi or self.task_name == "toolhang"):
@@ -164,7 +169,9 @@ class MAR(nn.Module):
             self.diffproploss = DiffActLoss(6 if self.umi else 9, Dd, diffloss_act_d, diffloss_act_w,
                                             num_sampling_steps, grad_checkpointing, n_frames=self.n_frames,
                                             act_model_type=action_model_params.get("act_model_type", "conv_fc"),
-                                            act_diff_training_steps=act_diff_training_steps)
+                                            act_diff_training_steps=act_diff_training_steps,
+                                            act_diff_testing_steps=act_diff_testing_steps, act_sampler=act_sampler,
+                                            act_ddim_eta=act_ddim_eta)
 
     # ---- init (mar_con_unified.py:349-391) ----------------------------------------------
     def initialize_weights(self):

@@ -17,6 +17,10 @@ MI355X layout of one sampling call over R = B*16 action rows and S spaced steps:
     for the final layer, and for fc1 at few rows),
     and the fused p_sample update kernel (uva_p_sample_step) -- replayed from a captured HIP graph after one eager step
     (which also settles the per-shape GEMM route choices before capture).
+The update rule is a choice of its own (method): "ddpm", the reference policy's ancestral p_sample, or "ddim",
+the eta-parameterised update the reference's diffusion class ships but its policy never calls
+(gaussian_diffusion.py:543-590; uva_ddim_step).  Either rule runs over either spacing form ("ddimN" strided,
+"N" even).  DDIM always takes the eager-first-step + captured-graph route.
 No autograd and no backward residues (the training trunk's aux tensors) are produced.
 """
 
@@ -47,14 +51,25 @@ class ActionSampler:
     # B*1024 tokens) the general 256x256-tile GEMMs are the right tool
     FUSED_MAX_ROWS = 1024
 
+    METHODS = ("ddpm", "ddim")
+
     def __init__(self, net, respacing="100", use_graph=True, use_fused=True, clip_denoised=True,
-                 use_persistent=True):
+                 use_persistent=True, method="ddpm", eta=0.0):
+        if method not in self.METHODS:
+            raise ValueError(f"unknown sampler {method!r}: expected one of {self.METHODS}")
         self.net = net
+        # update rule of the step, independent of the spacing: "ddpm" the ancestral learned-variance
+        # p_sample, "ddim" the eta-parameterised DDIM update (gaussian_diffusion.py:543-590; eta = 0
+        # deterministic: no per-step noise is drawn, copied or read)
+        self.method = method
+        self.eta = float(eta)
         # few rows (R <= 16: action sampling at B = 1): the whole loop as ONE persistent launch
         # (uva_sampler_persistent) instead of the captured ~15 launches per step
         self.use_persistent = use_persistent
         self.clip = clip_denoised  # action head: True (diffusion_action_loss.py:218); video head: False
         self.sched = sampling_schedule(respacing)
+        self.ddim = self.sched.ddim_steps(self.eta) if method == "ddim" else None
+        self.needs_step_noise = method == "ddpm" or self.eta != 0.0
         self.use_graph = use_graph
         self.use_fused = use_fused  # few-row fused LN+linear kernels (bf16 compute, width <= 1024)
         # LN inside fc1's A staging re-normalises the rows once per column block: at B=32 (512 rows)
@@ -142,6 +157,11 @@ class ActionSampler:
                                shift=fm[:, :W], scale=fm[:, W:2 * W])
         else:
             self._step_unfused(x, mod, st)
+        if self.method == "ddim":
+            coef = list(self.ddim[k][2]) + [st["temperature"]]
+            noise = st["noise"][k] if st["noise"] is not None and coef[4] != 0.0 else None
+            ops.ddim_step(st["out"], st["x"], noise, coef, st["x"], st["x_net"], clip=self.clip)
+            return
         coef = list(self.sched.steps[k][2]) + [st["temperature"]]
         ops.p_sample_step(st["out"], st["x"], st["noise"][k], coef, st["x"], st["x_net"], clip=self.clip)
 
@@ -168,7 +188,8 @@ class ActionSampler:
         cd = cdt()
         # RT.param_gen: the optimizer / EMA kernels rewrite weights without bumping _version, and the
         # captured graph and the concatenated modulation weights (wcat / bcat) must follow them
-        sig = (R, C, str(cd), float(temperature), str(dev), self.use_fused, self.use_persistent, RT.param_gen,
+        sig = (R, C, str(cd), float(temperature), str(dev), self.use_fused, self.use_persistent, self.method,
+               self.eta, RT.param_gen,
                tuple((p.data_ptr(), p._version) for p in net.parameters()))
         cache = getattr(self, "_cache", None)
         if cache is not None and cache["sig"] == sig:
@@ -182,15 +203,20 @@ class ActionSampler:
                   sy=torch.empty(S, R, W, dtype=cd, device=dev),
                   mod=None if per_step else torch.empty(S, R, ncol, dtype=cd, device=dev),
                   mod_buf=torch.empty(R, ncol, dtype=cd, device=dev) if per_step else None,
-                  x=torch.empty(R, C, dtype=F32, device=dev), noise=torch.empty(S, R, C, dtype=F32, device=dev),
+                  x=torch.empty(R, C, dtype=F32, device=dev),
+                  noise=torch.empty(S, R, C, dtype=F32, device=dev) if self.needs_step_noise else None,
                   x_net=torch.empty(R, C, dtype=cd, device=dev),
                   h0=torch.empty(R, W, dtype=F32, device=dev), h1=torch.empty(R, W, dtype=F32, device=dev),
                   h=torch.empty(R, W, dtype=cd, device=dev), a=torch.empty(R, W, dtype=cd, device=dev),
                   mean=torch.empty(R, dtype=F32, device=dev), rstd=torch.empty(R, dtype=F32, device=dev),
                   out=torch.empty(R, 2 * C, dtype=F32, device=dev), graph=None,
                   fused=self.use_fused and cd == torch.bfloat16 and W in (256, 512, 1024) and R <= self.FUSED_MAX_ROWS)
-        st["persist"] = (self.use_persistent and st["fused"] and st["mod"] is not None and R <= 16 and W == 1024
-                         and len(blocks) == 6 and C <= 16 and dev.type == "cuda"
+        # DDIM never takes the one-launch persistent kernel: that kernel's workgroup hand-offs are the one
+        # part of the sampler with a hang mode, and at ~10 steps the captured graph's launch chain is a
+        # few hundred microseconds at most above it (measured at B = 1: sample() 1.78 ms with ten DDIM steps on
+        # the graph route against 7.99 ms for the persistent kernel's 100 steps)
+        st["persist"] = (self.method == "ddpm" and self.use_persistent and st["fused"] and st["mod"] is not None
+                         and R <= 16 and W == 1024 and len(blocks) == 6 and C <= 16 and dev.type == "cuda"
                          and ops.sampler_persistent_fits(dev))
         if st["persist"]:
             # weights stacked per kind (one base pointer each), coefficient table [S, 8] on the device
@@ -213,11 +239,16 @@ class ActionSampler:
 
     @torch.no_grad()
     def __call__(self, c, noise, step_noise, temperature=1.0):
-        """c [R, z] fp32 cond, noise [R, C] x_T, step_noise [S, R, C] -> x_0 [R, C] fp32."""
+        """c [R, z] fp32 cond, noise [R, C] x_T, step_noise [S, R, C] -> x_0 [R, C] fp32.
+        method "ddim" with eta = 0: step_noise may be None and is ignored either way."""
         dev = c.device
         R, C = noise.shape
         S = self.sched.S
-        if step_noise.shape != (S, R, C):
+        if not self.needs_step_noise:
+            step_noise = None
+        elif step_noise is None:
+            raise ValueError(f"step_noise [S, R, C] is required (method {self.method}, eta {self.eta})")
+        if step_noise is not None and step_noise.shape != (S, R, C):
             raise ValueError(f"step_noise {tuple(step_noise.shape)} != {(S, R, C)}")
         if c.shape[0] != R:
             raise ValueError(f"cond rows {c.shape[0]} != noise rows {R}")
@@ -238,7 +269,8 @@ class ActionSampler:
             self.persistent_giveups = getattr(self, "persistent_giveups", 0) + 1
         st["x"].copy_(noise)
         st["x_net"].copy_(noise)
-        st["noise"].copy_(step_noise)
+        if step_noise is not None:
+            st["noise"].copy_(step_noise)
         self._step(0, st)  # eager: settles GEMM routes and workspaces before capture
         if S > 1 and self.use_graph and dev.type == "cuda":
             if st["graph"] is None:

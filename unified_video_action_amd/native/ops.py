@@ -463,6 +463,27 @@ def p_sample_step(out, x, noise, coef, x_new, x_net=None, clip=True):
                ptr(x_net), int(clip), rows, C, stream())
 
 
+def ddim_step(out, x, noise, coef, x_new, x_net=None, clip=True):
+    """One DDIM step (uva_ddim_step); coef = 6 python floats {k0, k1, a, b, s, temperature} of the step.
+    noise may be None when s == 0 (eta = 0, or the t = 0 step): the kernel does not read it then."""
+    rows, C = x.shape
+    if out.shape[0] != rows or out.shape[1] != 2 * C or out.stride(1) != 1:
+        raise ValueError(f"ddim_step: out {tuple(out.shape)} vs x {tuple(x.shape)}")
+    if len(coef) != 6:
+        raise ValueError(f"ddim_step: coef holds {len(coef)} values, not 6")
+    if noise is None and float(coef[4]) != 0.0:
+        raise ValueError("ddim_step: noise may be None only when s == 0")
+    for t in (x, x_new) + (() if noise is None else (noise,)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != x.shape:
+            raise ValueError("ddim_step: x / noise / x_new must be contiguous fp32 [rows, C]")
+    if x_net is not None and (not x_net.is_contiguous() or x_net.shape != x.shape):
+        raise ValueError("ddim_step: x_net must be contiguous [rows, C]")
+    k = (ctypes.c_float * 6)(*coef)
+    _call("uva_ddim_step", dt(out), ptr(out), out.stride(0), ptr(x), ptr(noise),
+               ctypes.cast(k, ctypes.c_void_p), ptr(x_new), dt(x_net) if x_net is not None else 0,
+               ptr(x_net), int(clip), rows, C, stream())
+
+
 def sampler_linear(A, W, out, bias=None, act="none", ln=False, lnw=None, lnb=None, shift=None, scale=None,
                    eps=1e-6, gate=None, residual=None):
     """Few-row fused linear (uva_sampler_linear): out = epi(A' @ W^T + bias), A' = A (bf16) or the

@@ -129,6 +129,8 @@ class UnifiedVideoActionPolicy(nn.Module):
             grad_checkpointing=_get(ap, "grad_checkpointing", False), predict_video=_get(ap, "predict_video", True),
             act_diff_training_steps=_get(ap, "act_diff_training_steps", 1000),
             act_diff_testing_steps=_get(ap, "act_diff_testing_steps", "100"),
+            act_sampler=_get(ap, "act_sampler", "ddpm"), act_ddim_eta=_get(ap, "act_ddim_eta", 0.0),
+            video_sampler=_get(ap, "video_sampler", "ddpm"), video_ddim_eta=_get(ap, "video_ddim_eta", 0.0),
             action_model_params=_plain(action_model_params), use_history_action=self.use_history_action,
             action_mask_ratio=kwargs.get("action_mask_ratio", 0.5), use_proprioception=self.use_proprioception,
             predict_wrist_img=kwargs.get("predict_wrist_img") or False,
