@@ -385,6 +385,32 @@ int uva_adamw_ema_guarded(float* p, const float* g, float* m, float* v, float* e
                           long long n_decay, float lr, float b1, float b2, float eps, float wd, int step,
                           float grad_scale, float ema_decay, const float* rec, hipStream_t stream);
 
+/* ---- frame-wise video metrics (opt-in epoch-end PSNR / SSIM; csrc/video_metrics.hip) ----------
+ * a, b: uint8 videos addressed as [N][T][H][W][3] through five ELEMENT strides each (stride_a / stride_b:
+ * HOST arrays {n, t, y, x, c}); any non-negative strides, so channels-last clips, planar [n, 3, T, H, W]
+ * grids and [:, ::4] views are read in place, and the two operands may differ in layout.  Per frame (n, t),
+ * at index n T + t:
+ *   sse       int64: sum over pixels and channels of (a - b)^2, exact
+ *   ssim_sum  double: sum over the 3 channels and the (H - 10)(W - 10) valid window positions of
+ *             ((2 mua mub + C1)(2 sab + C2)) / ((mua^2 + mub^2 + C1)(saa + sbb + C2)),  C1 = 6.5025, C2 = 58.5225
+ *             (Wang et al. 2004 on 0..255 data), with mu = E[x], sxy = E[xy] - mux muy (population moments)
+ *             under the separable 11 x 11 window g (x) g.
+ * window: HOST array of 11 doubles g (the caller forms exp(-(i - 5)^2 / 4.5) / sum in float64, so a reference
+ * uses bit-identical weights).  All moments and the index are fp64.  Deterministic: per-tile partials in
+ * `work`, added per frame in a fixed order, no atomics -- a relaunch is bit-equal and the workspace need not
+ * be cleared.  Equal VALUES in a and b (at any addresses / strides) give exactly sse = 0 and
+ * ssim_sum = 3 (H - 10)(W - 10).  sse, ssim_sum and work are 8-byte aligned; a and b need no alignment.
+ * uva_frame_metrics_workspace_bytes: bytes of `work` (pure host; -1 for a refused shape).
+ * uva_frame_metrics_tile: the tile of window positions one workgroup covers (pure host).
+ * Refused (hipErrorInvalidValue, nothing launched or written): H < 11, W < 11, N <= 0 or T <= 0, a null
+ * operand / stride table / window / output / workspace, work_bytes below the query, a negative stride,
+ * a misaligned output or workspace. */
+int uva_frame_metrics_tile(int* th, int* tw);
+long long uva_frame_metrics_workspace_bytes(int N, int T, int H, int W);
+int uva_frame_metrics(const void* a, const long long* stride_a, const void* b, const long long* stride_b,
+                      const double* window, int N, int T, int H, int W, long long* sse, double* ssim_sum,
+                      void* work, long long work_bytes, hipStream_t stream);
+
 /* ---- fp8 (OCP e4m3) attention forward, head_dim 64 (BASELINE config 5 "fp8 MFMA attention";
  *      same call site as uva_attn_fwd: timm Attention / SDPA, mar_con_unified.py:201-249).
  * uva_attn_quant_fp8: per (batch, head, q|k|v, 64-row tile) power-of-two scales; rounds the bf16

@@ -1,7 +1,8 @@
-"""FVD of a checkpoint on N validation clips, or the I3D tower's own time.
+"""FVD and frame-wise PSNR / SSIM of a checkpoint on N validation clips, or the I3D tower's own time.
 
     python tools/fvd_eval.py --config-name=uva_pusht --i3d PATH [--checkpoint CKPT] [--clips 64]
-                             [--precision fp32|bf16] [key=value ...]
+                             [--precision fp32|bf16] [--metrics] [key=value ...]
+    python tools/fvd_eval.py --config-name=uva_pusht --metrics --no-fvd [--checkpoint CKPT] [--clips 64] [key=value ...]
     python tools/fvd_eval.py --tower-only --clips 256 --precision bf16 [--random-i3d] [--layers]
 
 The first form builds the workspace of train.py for the config, loads the checkpoint (latest.ckpt of the run
@@ -9,6 +10,13 @@ directory when none is given and one exists), and runs eval.test_video_fvd on th
 training.use_ema) over as many validation batches as N clips need -- N is not capped at the epoch-end
 evaluation's 16.  One JSON line: {"video_fvd", "clips", "precision", "tower_ms", "tower_calls"}; tower_ms is the
 time spent in the I3D tower (HIP events around every call).
+--metrics adds the frame-wise fidelity of the predicted future frames against the real ones (eval/video_metrics.py;
+no weights needed): "video_psnr", "video_ssim" (means over every frame; a perfect frame counts at the PSNR of one
+wrong level) and the per-horizon lists "video_psnr_t", "video_ssim_t".  --no-fvd (with --metrics)
+skips the tower, and --i3d is then not required.  Two samplers on the same clips (the validation loader is not
+shuffled; AP=model.policy.autoregressive_model_params):
+    python tools/fvd_eval.py --metrics --no-fvd --checkpoint CKPT +$AP.video_sampler=ddpm
+    python tools/fvd_eval.py --metrics --no-fvd --checkpoint CKPT +$AP.video_sampler=ddim +$AP.num_sampling_steps=ddim10
 --tower-only times the tower alone on N random uint8 clips [N, 16, 256, 256, 3] (one warm-up pass, then one
 timed pass between events): {"clips", "precision", "tower_ms", "ms_per_clip"}; --layers adds the time and the
 TFLOP/s of every conv3d / gemm shape from the ops trace of a further pass.
@@ -100,12 +108,25 @@ def checkpoint_fvd(args, overrides):
     vkw = dict(cfg.val_dataloader)
     loader = torch.utils.data.DataLoader(ws.dataset.get_validation_dataset(), **vkw)
     bs = int(vkw.get("batch_size", 1))
-    timed = TimedTower(build_tower(args, ws.device))
-    log = E.test_video_fvd(cfg, policy, loader, ws.epoch, args.output_dir, ws.device, i3d=timed,
-                           n_examples=-(-args.clips // bs), clips_per_batch=bs)
-    print(json.dumps({"video_fvd": log["video_fvd"], "clips": min(args.clips, len(loader.dataset)),
-                      "precision": args.precision, "tower_ms": round(timed.total_ms(), 3),
-                      "tower_calls": len(timed.events)}))
+    timed = None if args.no_fvd else TimedTower(build_tower(args, ws.device))
+    log = E.test_video_eval(cfg, policy, loader, ws.epoch, args.output_dir, ws.device, i3d=timed,
+                            n_examples=-(-args.clips // bs), clips_per_batch=bs, fvd=timed is not None,
+                            metrics=args.metrics)
+    out = {"clips": min(args.clips, len(loader.dataset))}
+    if timed is not None:
+        out.update({"video_fvd": log["video_fvd"], "precision": args.precision,
+                    "tower_ms": round(timed.total_ms(), 3), "tower_calls": len(timed.events)})
+    if args.metrics:
+        out.update(metrics_json(log))
+    print(json.dumps(out))
+
+
+def metrics_json(log):
+    """the metric log keys of eval.test_video_eval -> the JSON line's entries (per-horizon values as lists)"""
+    h = sum(1 for k in log if k.startswith("video_psnr/t"))
+    return {"video_psnr": log["video_psnr"], "video_ssim": log["video_ssim"],
+            "video_psnr_t": [log[f"video_psnr/t{t}"] for t in range(1, h + 1)],
+            "video_ssim_t": [log[f"video_ssim/t{t}"] for t in range(1, h + 1)]}
 
 
 def main(argv=None):
@@ -120,9 +141,13 @@ def main(argv=None):
     ap.add_argument("--output-dir", default=None, help="where the real / predicted grids go (.npy); none by default")
     ap.add_argument("--tower-only", action="store_true")
     ap.add_argument("--layers", action="store_true")
+    ap.add_argument("--metrics", action="store_true", help="add the frame-wise PSNR / SSIM of the predicted frames")
+    ap.add_argument("--no-fvd", action="store_true", help="with --metrics: skip the I3D tower (no --i3d needed)")
     args, overrides = ap.parse_known_args(argv)
-    if not args.random_i3d and not args.i3d:
-        ap.error("--i3d PATH (or --random-i3d for timing) is required")
+    if args.no_fvd and (not args.metrics or args.tower_only):
+        ap.error("--no-fvd goes with --metrics (and not with --tower-only): nothing would be evaluated")
+    if not args.no_fvd and not args.random_i3d and not args.i3d:
+        ap.error("--i3d PATH (or --random-i3d for timing) is required unless --metrics --no-fvd is given")
     if not torch.cuda.is_available():
         raise SystemExit("fvd_eval.py needs the GPU: the tower runs on libuva_hip.so kernels")
     if args.tower_only:

@@ -8,6 +8,9 @@ test_video_fvd   n_examples = 4 validation batches, k = min(4, B) clips each: th
 test_action_l2   every validation batch: sample_tokens(task_mode="policy_model"), both trajectories
                  unnormalized, mean L2 over the first 9 action dimensions.
 Both return the reference's log keys (`video_fvd`, `val_action_l2_distances`, prefixed by name_label).
+test_video_eval  the loop of test_video_fvd, serving the FVD, the frame-wise PSNR / SSIM of the predicted future
+                 frames against the real ones (video_metrics.py; not in the reference) or both from one pass of
+                 clip generation; test_video_fvd is test_video_eval with the metrics off.
 
 Differences from the reference: the I3D tower is this build's HIP one (fvd/i3d.py) and is passed in (or
 loaded from the LOCAL file training.i3d_pretrained_path -- nothing is downloaded); no GIF / wandb video is
@@ -129,14 +132,25 @@ def _load_i3d(cfg, device):
 
 
 @torch.no_grad()
-def test_video_fvd(cfg, policy, loader, it, output_dir, device, name_label="", plot_actions=False, i3d=None, rng=None,
-                   keep=None, n_examples=N_EXAMPLES, clips_per_batch=N_EXAMPLES):
-    """-> {name_label + "video_fvd": float}.  keep: an optional dict that receives the uint8 clips the tower saw
-    (real_clips / pred_clips [n, 16, 256, 256, 3]) and their logits (real_embeddings / pred_embeddings).
-    n_examples batches of min(clips_per_batch, B) clips are evaluated: the reference's 4 x 4 by default
-    (tools/fvd_eval.py raises both for larger evaluations)."""
-    if i3d is None:
+def test_video_eval(cfg, policy, loader, it, output_dir, device, name_label="", i3d=None, rng=None, keep=None,
+                    n_examples=N_EXAMPLES, clips_per_batch=N_EXAMPLES, fvd=True, metrics=False):
+    """One pass of clip generation that serves the FVD (fvd=True), the frame-wise metrics (metrics=True) or both.
+    -> the log entries: name_label + "video_fvd" with fvd; with metrics name_label + "video_psnr", "video_ssim"
+    (means over every predicted frame) and "video_psnr/t1" .. "/t{h}", "video_ssim/t1" .. "/t{h}" (means per
+    prediction horizon; eval/video_metrics.aggregate, whose PSNR cap for perfect frames applies).
+    The metrics compare exactly the uint8 future frames the tower sees, pred against real [k, h, 256, 256, 3],
+    before the x4 repeat; they draw nothing, so with both on the FVD is the FVD with metrics off.
+    keep: an optional dict that receives the uint8 clips the tower saw (real_clips / pred_clips
+    [n, 16, 256, 256, 3]), the saved grids, with fvd the logits (real_embeddings / pred_embeddings) and with
+    metrics the per-frame psnr / ssim [n, h].  i3d: the tower (loaded from training.i3d_pretrained_path when
+    absent); not needed, and not loaded, with fvd=False."""
+    if not (fvd or metrics):
+        raise ValueError("test_video_eval: nothing to evaluate (fvd and metrics are both off)")
+    if fvd and i3d is None:
         i3d = _load_i3d(cfg, device)
+    if metrics:
+        from . import video_metrics as VM
+    frame_psnr, frame_ssim = [], []
     real_emb, pred_emb, reals, predictions, real_clips, pred_clips = [], [], [], [], [], []
     for n, batch in enumerate(loader):
         if n >= n_examples:
@@ -153,6 +167,10 @@ def test_video_fvd(cfg, policy, loader, it, output_dir, device, name_label="", p
         pred = policy.vae_model.decode(z / LATENT_SCALE).clamp(-1, 1).cpu()
         pred = to_uint8(pred.reshape(k, -1, *pred.shape[1:]).permute(0, 1, 3, 4, 2))   # b t h w c
         real = to_uint8(d["real"].permute(0, 2, 3, 4, 1).cpu())
+        if metrics:
+            m = VM.psnr_ssim(pred.to(device), real.to(device))
+            frame_psnr.append(m["psnr"])
+            frame_ssim.append(m["ssim"])
         x = to_uint8(d["x"].cpu())                                                        # b c t h w
         hist = x[:, :, :x.size(2) // 2]
         reals.append(torch.cat([hist, real.permute(0, 4, 1, 2, 3)], dim=2))
@@ -161,22 +179,43 @@ def test_video_fvd(cfg, policy, loader, it, output_dir, device, name_label="", p
             pred = pred.repeat_interleave(repeats=4, dim=1)
             real = real.repeat_interleave(repeats=4, dim=1)
         pred, real = pred.contiguous(), real.contiguous()
-        pred_emb.append(get_fvd_logits(pred, i3d).cpu())
-        real_emb.append(get_fvd_logits(real, i3d).cpu())
+        if fvd:
+            pred_emb.append(get_fvd_logits(pred, i3d).cpu())
+            real_emb.append(get_fvd_logits(real, i3d).cpu())
         real_clips.append(real)
         pred_clips.append(pred)
-    if not real_emb:
+    if not real_clips:
         raise ValueError("test_video_fvd: the validation loader is empty")
-    real_emb, pred_emb = torch.cat(real_emb), torch.cat(pred_emb)
-    fvd = float(frechet_distance(pred_emb, real_emb))
+    log = {}
+    if fvd:
+        real_emb, pred_emb = torch.cat(real_emb), torch.cat(pred_emb)
+        log[f"{name_label}video_fvd"] = float(frechet_distance(pred_emb, real_emb))
+    if metrics:
+        frame_psnr, frame_ssim = torch.cat(frame_psnr), torch.cat(frame_ssim)
+        log.update(VM.log_entries(VM.aggregate({"psnr": frame_psnr, "ssim": frame_ssim},
+                                               n_values=real_clips[0][0, 0].numel()), name_label))
     if output_dir is not None:
         os.makedirs(os.path.join(output_dir, "vis"), exist_ok=True)
         np.save(os.path.join(output_dir, "vis", f"{name_label}real_{it}.npy"), torch.cat(reals).numpy())
         np.save(os.path.join(output_dir, "vis", f"{name_label}predicted_{it}.npy"), torch.cat(predictions).numpy())
     if keep is not None:
-        keep.update(real_clips=torch.cat(real_clips), pred_clips=torch.cat(pred_clips), real_embeddings=real_emb,
-                    pred_embeddings=pred_emb, real_grid=torch.cat(reals), pred_grid=torch.cat(predictions))
-    return {f"{name_label}video_fvd": fvd}
+        keep.update(real_clips=torch.cat(real_clips), pred_clips=torch.cat(pred_clips), real_grid=torch.cat(reals),
+                    pred_grid=torch.cat(predictions))
+        if fvd:
+            keep.update(real_embeddings=real_emb, pred_embeddings=pred_emb)
+        if metrics:
+            keep.update(psnr=frame_psnr, ssim=frame_ssim)
+    return log
+
+
+def test_video_fvd(cfg, policy, loader, it, output_dir, device, name_label="", plot_actions=False, i3d=None, rng=None,
+                   keep=None, n_examples=N_EXAMPLES, clips_per_batch=N_EXAMPLES):
+    """-> {name_label + "video_fvd": float}.  keep: an optional dict that receives the uint8 clips the tower saw
+    (real_clips / pred_clips [n, 16, 256, 256, 3]) and their logits (real_embeddings / pred_embeddings).
+    n_examples batches of min(clips_per_batch, B) clips are evaluated: the reference's 4 x 4 by default
+    (tools/fvd_eval.py raises both for larger evaluations).  test_video_eval with the metrics off."""
+    return test_video_eval(cfg, policy, loader, it, output_dir, device, name_label=name_label, i3d=i3d, rng=rng,
+                           keep=keep, n_examples=n_examples, clips_per_batch=clips_per_batch, fvd=True, metrics=False)
 
 
 @torch.no_grad()

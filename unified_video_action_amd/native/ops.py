@@ -990,3 +990,82 @@ def fvd_preprocess(videos, out, size=224):
             tuple(out.shape[:4]) != (B, T, size, size) or videos.device != out.device:
         raise ValueError(f"fvd_preprocess: videos {tuple(videos.shape)} {videos.dtype}, out {tuple(out.shape)}")
     _call("uva_fvd_preprocess", ptr(videos), dt(out), ptr(out), B, T, H, W, size, out.shape[4], stream())
+
+
+def ssim_window():
+    """the 11 taps g[i] = exp(-(i - 5)^2 / (2 1.5^2)) / sum of the SSIM window, float64 (numpy), as frame_metrics
+    passes them to the kernel: a reference that forms them by the same expression holds the same bits"""
+    import numpy as np
+    i = np.arange(11, dtype=np.float64) - 5.0
+    g = np.exp(-(i * i) / (2.0 * 1.5 ** 2))
+    return g / g.sum()
+
+
+def frame_metrics_tile():
+    """(th, tw): the tile of window positions one workgroup of frame_metrics covers (pure host)"""
+    th, tw = ctypes.c_int(0), ctypes.c_int(0)
+    lib().call("uva_frame_metrics_tile", ctypes.addressof(th), ctypes.addressof(tw))
+    return th.value, tw.value
+
+
+def frame_metrics_workspace_bytes(N, T, H, W):
+    r = lib().query("uva_frame_metrics_workspace_bytes", int(N), int(T), int(H), int(W))
+    if r < 0:
+        raise ValueError(f"frame_metrics_workspace_bytes: refused shape N {N} T {T} H {H} W {W}")
+    return r
+
+
+def _frame_metrics_view(name, v, channels):
+    """-> the [n, T, H, W, 3] view of a 5-D uint8 video whose dimension `channels` holds the 3 channels"""
+    if not torch.is_tensor(v) or v.dtype != torch.uint8:
+        raise ValueError(f"frame_metrics: {name} must be a uint8 tensor, not "
+                         f"{v.dtype if torch.is_tensor(v) else type(v).__name__}")
+    if v.dim() != 5:
+        raise ValueError(f"frame_metrics: {name} {tuple(v.shape)} is not a 5-D video")
+    if not -5 <= channels < 5:
+        raise ValueError(f"frame_metrics: channels={channels} is not a dimension of a 5-D video")
+    c = channels % 5
+    if v.shape[c] != 3:
+        raise ValueError(f"frame_metrics: dimension {channels} of {name} {tuple(v.shape)} holds {v.shape[c]} "
+                         "channels, not 3")
+    return v.movedim(c, 4) if c != 4 else v
+
+
+def frame_metrics(a, b, channels=-1, sse=None, ssim_sum=None, work=None):
+    """Per-frame squared error and SSIM sum of two uint8 videos on the device (uva_frame_metrics).
+    a, b: equal-shape uint8 tensors [n, T, H, W, 3] -- or with the 3 channels in dimension `channels`, the other
+    four staying in the order n, T, H, W (channels=1: the planar [n, 3, T, H, W] grids) -- of any strides: they
+    are read in place, nothing is copied.  -> (sse int64 [n, T] exact, ssim_sum float64 [n, T]: the SSIM index
+    summed over the 3 channels and the (H - 10)(W - 10) valid window positions).  sse / ssim_sum / work:
+    optional preallocated contiguous outputs and a workspace of >= frame_metrics_workspace_bytes bytes."""
+    va, vb = _frame_metrics_view("a", a, channels), _frame_metrics_view("b", b, channels)
+    if va.shape != vb.shape:
+        raise ValueError(f"frame_metrics: a {tuple(a.shape)} and b {tuple(b.shape)} differ in shape")
+    N, T, H, W, _ = va.shape
+    if H < 11 or W < 11 or N * T <= 0:
+        raise ValueError(f"frame_metrics: {tuple(va.shape)} holds no 11 x 11 window (or no frame)")
+    if not (va.is_cuda and vb.is_cuda and va.device == vb.device):
+        raise ValueError("frame_metrics: a and b must be on one GPU (there is no CPU path)")
+    if min(va.stride()) < 0 or min(vb.stride()) < 0:
+        raise ValueError("frame_metrics: negative strides")
+    if sse is None:
+        sse = torch.empty(N, T, dtype=torch.int64, device=va.device)
+    if ssim_sum is None:
+        ssim_sum = torch.empty(N, T, dtype=torch.float64, device=va.device)
+    if sse.dtype != torch.int64 or ssim_sum.dtype != torch.float64 or tuple(sse.shape) != (N, T) or \
+            tuple(ssim_sum.shape) != (N, T) or not sse.is_contiguous() or not ssim_sum.is_contiguous() or \
+            sse.device != va.device or ssim_sum.device != va.device:
+        raise ValueError(f"frame_metrics: sse (int64) / ssim_sum (float64) must be contiguous [{N}, {T}] on "
+                         f"{va.device}")
+    need = frame_metrics_workspace_bytes(N, T, H, W)
+    if work is None:
+        work = torch.empty(need // 8, dtype=torch.float64, device=va.device)
+    if not torch.is_tensor(work) or work.device != va.device or not work.is_contiguous() or \
+            work.numel() * work.element_size() < need:
+        raise ValueError(f"frame_metrics: work must be a contiguous buffer of >= {need} bytes on {va.device}")
+    sa = (ctypes.c_longlong * 5)(*va.stride())
+    sb = (ctypes.c_longlong * 5)(*vb.stride())
+    g = (ctypes.c_double * 11)(*ssim_window().tolist())
+    _call("uva_frame_metrics", ptr(va), ctypes.addressof(sa), ptr(vb), ctypes.addressof(sb), ctypes.addressof(g),
+          N, T, H, W, ptr(sse), ptr(ssim_sum), ptr(work), work.numel() * work.element_size(), stream())
+    return sse, ssim_sum

@@ -91,9 +91,9 @@ class TopKCheckpointManager:
             key, mode, fmt = self.monitor_key, self.mode, self.format_str
         else:
             # Difference from the reference (which raises KeyError): test_mean_score comes from env-runner
-            # rollouts this workspace does not run, and video_fvd / val_action_l2_distances are logged only
-            # when the epoch-end evaluation is switched on (training.i3d_pretrained_path /
-            # training.eval_action_l2), so a call without the configured key ranks by train_loss (min)
+            # rollouts this workspace does not run, and video_fvd / val_action_l2_distances / video_psnr /
+            # video_ssim are logged only when the epoch-end evaluation is switched on (training.i3d_pretrained_path
+            # / training.eval_action_l2 / training.eval_video_metrics), so a call without the configured key ranks by train_loss (min)
             # under a file name that says so -- per call, in a ranking of its own: the configured key,
             # once logged, is used again
             if self.FALLBACK[0] not in data:
@@ -279,7 +279,7 @@ class TrainUnifiedVideoActionWorkspace(BaseWorkspace):
         # epoch-end evaluation (workspace:342-376), rank 0 only, off unless asked for
         self.val_dataloader, self.i3d = None, None
         run_fvd, run_l2 = self.eval_plan()
-        if (run_fvd or run_l2) and self.rank == 0:
+        if (run_fvd or run_l2 or self.eval_video_metrics()) and self.rank == 0:
             vkw = dict(cfg.val_dataloader)
             if not torch.cuda.is_available():
                 vkw["pin_memory"] = False
@@ -303,10 +303,19 @@ class TrainUnifiedVideoActionWorkspace(BaseWorkspace):
             bool(cfg.training.get("eval_action_l2", False))
         return run_fvd, run_l2
 
+    def eval_video_metrics(self):
+        """the third decision, beside eval_plan()'s two: frame-wise PSNR / SSIM of the predicted future frames
+        (eval/video_metrics.py) when the policy predicts video AND training.eval_video_metrics is set.  Needs no
+        I3D weights: without training.i3d_pretrained_path no tower is built and only the metrics are logged"""
+        cfg = self.cfg
+        return bool(cfg.model.policy.autoregressive_model_params.get("predict_video", True)) and \
+            bool(cfg.training.get("eval_video_metrics", False))
+
     def evaluate_epoch(self, rng=None):
         """-> the evaluation's log entries ({} when nothing is switched on or on a rank other than 0)"""
         run_fvd, run_l2 = self.eval_plan()
-        if not (run_fvd or run_l2) or self.rank != 0:
+        run_vm = self.eval_video_metrics()
+        if not (run_fvd or run_l2 or run_vm) or self.rank != 0:
             return {}
         from ..eval import eval as E
         cfg = self.cfg
@@ -314,7 +323,10 @@ class TrainUnifiedVideoActionWorkspace(BaseWorkspace):
         policy.eval()
         log = {}
         try:
-            if run_fvd:
+            if run_vm:   # one pass of clip generation for the metrics and, when on, the FVD
+                log.update(E.test_video_eval(cfg, policy, self.val_dataloader, self.epoch, self.output_dir,
+                                             self.device, i3d=self.i3d, rng=rng, fvd=run_fvd, metrics=True))
+            elif run_fvd:
                 log.update(E.test_video_fvd(cfg, policy, self.val_dataloader, self.epoch, self.output_dir, self.device,
                                             i3d=self.i3d, rng=rng))
             if run_l2:
